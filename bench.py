@@ -20,6 +20,8 @@ oracle (a port of the reference's forward + autograd backward) on a bounded samp
 Other workloads of BASELINE.json (`--arch`): vit_s_16 (configs[1]), vit_l_16 (configs[3], batch 128), mae_b_16
 (configs[4]: MAE over a ViT-B/16 encoder, 75 % mask -> 49 encoder tokens), the SimpleViT family; `--robust` selects the
 Sinkhorn attention (the reference's `robust=True`), `--noise-std S` the noisy-input training of examples/nowak.py:153.
+`--dump-outputs DIR` writes what the last timed step computed (loss, updated parameters, gradients; dump_outputs()) so that
+two builds can be compared output for output: the inputs and the initial weights are seeded.
 """
 from __future__ import annotations
 
@@ -182,6 +184,32 @@ def cpu_baseline(arch: str, robust: bool, budget_s: float = 24.0):
                       f"{n32} steps, bf16 median of {n16} steps, 1 warm-up each"}
 
 
+DUMP_SAMPLE = 1 << 22      # elements per sampled array: 16 MiB of float32 each
+
+
+def dump_outputs(out_dir: str, model: torch.nn.Module, loss: torch.Tensor, sample: int = DUMP_SAMPLE, seed: int = 0) -> dict:
+    """What one training step hands its caller, from the last timed step, as float32 .npy files under `out_dir`: the loss,
+    the parameters after the update and the gradients the update used.  Parameters and gradients are flattened in
+    named_parameters() order; past `sample` elements one element per equal stratum is kept, at a seeded offset, so the
+    positions are the same in both files and in every run.  Returns {name: shape}."""
+    import numpy as np
+    params = [p for _, p in model.named_parameters() if p.requires_grad]
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    flat_g = torch.cat([(p.grad.detach().reshape(-1).float() if p.grad is not None else torch.zeros_like(p, dtype=torch.float32).reshape(-1))
+                        for p in params])
+    n = flat_p.numel()
+    if n > sample:
+        bounds = np.arange(sample + 1, dtype=np.int64) * n // sample
+        idx = bounds[:-1] + (np.random.default_rng(seed).random(sample) * np.diff(bounds)).astype(np.int64)
+        idx = torch.from_numpy(idx).to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    arrays = {"loss": loss.detach().float().reshape(1), "params": flat_p, "grads": flat_g}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+    return {name: list(t.shape) for name, t in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -205,7 +233,11 @@ def main():
     ap.add_argument("--wgrad", default="default", choices=["default", "grouped", "single"],
                     help="weight gradients: one grouped stream-K launch per layer, or one split-K launch per gradient (A/B switch)")
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured HIP graph (Trainer.capture)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss, parameters and gradients (seeded sample) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ          # started by torch.distributed.run
     rank = int(os.environ.get("RANK", "0"))
@@ -276,6 +308,7 @@ def main():
     elapsed = time.perf_counter() - t0
     per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     med = statistics.median(per_step)
+    dumped = dump_outputs(args.dump_outputs, model, loss) if args.dump_outputs and rank == 0 else None
     if world > 1:
         t = torch.tensor([elapsed, med], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -318,6 +351,8 @@ def main():
         "gflop_per_image": gflop_img,
         "loss": round(float(loss), 4),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
 
     if rank == 0 and not args.no_roofline and world == 1:
         # instrumented steps: HIP events around every C-ABI launch on the compute stream

@@ -287,3 +287,34 @@ def test_capture_recorder_names_the_replay_unsafe_library_ops():
 
     assert _record_unsafe_ops(bad) == {"aten.embedding_dense_backward", "aten.index_put(accumulate=True)"}
     assert _record_unsafe_ops(fine) == set()
+
+
+def test_bench_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: loss, parameters and gradients as float32 .npy; past the sample size the same seeded
+    positions every time, in both files."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(16, 8), torch.nn.Linear(8, 4))
+    loss = m(torch.randn(3, 16)).square().mean()
+    loss.backward()
+    flat_p = torch.cat([p.detach().reshape(-1) for p in m.parameters()])
+    flat_g = torch.cat([p.grad.reshape(-1) for p in m.parameters()])
+
+    shapes = bench.dump_outputs(str(tmp_path / "all"), m, loss)
+    assert shapes == {"loss": [1], "params": [flat_p.numel()], "grads": [flat_g.numel()]}
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in shapes}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["params"], flat_p.numpy()) and np.array_equal(got["grads"], flat_g.numpy())
+    assert got["loss"][0] == np.float32(loss.item())
+
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), m, loss, sample=50)
+    a, b = (np.load(tmp_path / run / "params.npy") for run in ("a", "b"))
+    assert a.shape == (50,) and np.array_equal(a, b)
+    # every sampled element is a real parameter, and the gradient file samples the same positions
+    pos = [int(np.flatnonzero(flat_p.numpy() == v)[0]) for v in a]
+    assert pos == sorted(pos) and len(set(pos)) == 50
+    assert np.array_equal(np.load(tmp_path / "a" / "grads.npy"), flat_g.numpy()[pos])

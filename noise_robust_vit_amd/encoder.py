@@ -21,7 +21,7 @@ from __future__ import annotations
 import functools
 import weakref
 from dataclasses import dataclass
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -134,7 +134,7 @@ class BlockMeta:
     # oracle uses; default: torch's device generator).  Sites of layer i: 3 i (attention branch), 3 i + 1 (GELU output), 3 i + 2 (MLP branch).
     dropout: float = 0.0
     mask_source: Optional[object] = None
-    # dropout on the attention weights (vit.py:108): composed on the materialised [B,H,N,N] matrix (kernels.attn_dropout_fwd), site -(2 + i)
+    # dropout on the attention weights (vit.py:108): composed on the materialised [B,H,N,N] matrix (kernels.attn_composed_fwd), site -(2 + i)
     attn_dropout: float = 0.0
     # additive score bias of ONE call (attention / key-padding masks of the stand-alone MultiheadAttention, utils.py:741-751): fp32,
     # broadcastable to [B, H, N, N], -inf = masked; composed path
@@ -307,20 +307,26 @@ class record_attention:
         _RECORDING = self._prev
 
 
-def _record(qkv: Tensor, aux, B: int, N: int, H: int, dh: int, scale: float, robust: bool) -> None:
-    if robust:
-        lse, scal = aux[0], aux[1]                        # scalings [B, H, 7, N]: a1 b1 a2 b2 a3 b3 a4
-        p = K.attn_probs(qkv, lse, B, N, H, dh, scale)
-        a, b = scal[:, :, 6], scal[:, :, 5]              # the vectors are cumulative: P = diag(a4) softmax(S) diag(b3)
+def _record(qkv: Tensor, att: AttnSaved, B: int, N: int, H: int, dh: int, scale: float) -> None:
+    p = K.attn_probs(qkv, att.lse, B, N, H, dh, scale)
+    if att.kind == "sinkhorn":                            # scalings [B, H, 7, N]: a1 b1 a2 b2 a3 b3 a4
+        a, b = att.scal[:, :, 6], att.scal[:, :, 5]      # the vectors are cumulative: P = diag(a4) softmax(S) diag(b3)
         p = p * a[..., :, None] * b[..., None, :]
-    else:
-        p = K.attn_probs(qkv, aux, B, N, H, dh, scale)
     _RECORDING.append(p)
 
 
 # ----------------------------------------------------------------------------------------------
 # attention half
 # ----------------------------------------------------------------------------------------------
+class AttnSaved(NamedTuple):
+    """Saved attention state and the path that wrote it: "softmax" (lse), "sinkhorn" (robust=True: lse, scal, and in `saved` the
+    P7 dict of kernels.attn_sinkhorn_fwd) or "composed" (weight dropout / score bias: kernels.ComposedSaved in `saved`)."""
+    kind: str
+    lse: Optional[Tensor] = None
+    scal: Optional[Tensor] = None
+    saved: object = None
+
+
 def draw_keep(meta: BlockMeta, site: int, shape, device, p: Optional[float] = None) -> Tensor:
     """uint8 keep mask of one dropout site (1 = kept); p defaults to the stack's `dropout`."""
     if meta.mask_source is not None:
@@ -349,16 +355,17 @@ def attn_half_fwd(x: Tensor, B: int, N: int, meta: BlockMeta, ln_w, ln_b, wqkv, 
         if adrop is not None:
             pscale, asite, pa = adrop
             akeep = draw_keep(meta, asite, (B, H, N, N), x.device, p=pa)
-        o, asaved = K.attn_dropout_fwd(qkv, B, N, H, dh, scale, meta.robust, akeep, pscale, bias=meta.attn_bias)
-        aux = ("attn_dropout", asaved)
+        o, cs = K.attn_composed_fwd(qkv, B, N, H, dh, scale, 3 if meta.robust else 0, akeep, pscale, bias=meta.attn_bias)
+        att = AttnSaved("composed", saved=cs)
     elif meta.robust:                             # robust=True: softmax + Sinkhorn normalisation (utils.py:1025-1037), fused
         p7 = {}                                   # the composed path (N > 256 / dh != 64) hands its P7 to the backward through it
         o, lse, scal = K.attn_sinkhorn_fwd(qkv, B, N, H, dh, scale, saved=p7)
-        aux = (lse, scal, p7)
+        att = AttnSaved("sinkhorn", lse, scal, p7)
     else:
-        o, aux = K.attn_fwd(qkv, B, N, H, dh, scale)
-    if _RECORDING is not None and adrop is None and meta.attn_bias is None:
-        _record(qkv, aux, B, N, H, dh, scale, meta.robust)
+        o, lse = K.attn_fwd(qkv, B, N, H, dh, scale)
+        att = AttnSaved("softmax", lse)
+    if _RECORDING is not None and att.kind != "composed":
+        _record(qkv, att, B, N, H, dh, scale)
     keep = None
     if residual and drop is not None:
         # dropout on the branch output (vit.py:125): the bias epilogue writes the branch, one pass adds what is kept to the stream
@@ -374,7 +381,7 @@ def attn_half_fwd(x: Tensor, B: int, N: int, meta: BlockMeta, ln_w, ln_b, wqkv, 
             scale, site = drop
             keep = draw_keep(meta, site, y.shape, x.device)
             K.mask_mul_f32(y, keep, scale, out=y)
-    return y, (x, xn, mean, rstd, qkv, o, aux, keep)
+    return y, (x, xn, mean, rstd, qkv, o, att, keep)
 
 
 def attn_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, B: int, N: int, meta: BlockMeta,
@@ -382,7 +389,7 @@ def attn_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, B: int,
     """Returns (dx32|None, dx16|None, [d ln_w, d ln_b, d wqkv, d bqkv, d wo, d bo]).
 
     The incoming gradient is given as fp32 (`dy32`), bf16 (`dy16`) or both; the residual add uses fp32 when present."""
-    x, xn, mean, rstd, qkv, o, aux, keep = saved
+    x, xn, mean, rstd, qkv, o, att, keep = saved
     H, dh = meta.heads, meta.dim_head
     if dy16 is None:
         dy16 = K.cast_bf16(dy32)
@@ -394,12 +401,12 @@ def attn_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, B: int,
     dwo, dbo = _dw_db(meta, dy16, o, wo, bo)
     do = K.gemm_nt(dy16, wo_t, out_dtype=torch.bfloat16)
     scale = dh ** -0.5
-    if isinstance(aux, tuple) and len(aux) == 2 and isinstance(aux[0], str):         # ("attn_dropout", saved)
-        dqkv = K.attn_dropout_bwd(qkv, do, aux[1], B, N, H, dh, scale)
-    elif meta.robust:
-        dqkv = K.attn_sinkhorn_bwd(qkv, do, aux[0], aux[1], B, N, H, dh, scale, saved=aux[2])
+    if att.kind == "composed":
+        dqkv = K.attn_composed_bwd(qkv, do, att.saved, B, N, H, dh, scale)
+    elif att.kind == "sinkhorn":
+        dqkv = K.attn_sinkhorn_bwd(qkv, do, att.lse, att.scal, B, N, H, dh, scale, saved=att.saved)
     else:
-        dqkv = K.attn_bwd(qkv, o, do, aux, B, N, H, dh, scale)
+        dqkv = K.attn_bwd(qkv, o, do, att.lse, B, N, H, dh, scale)
     dwqkv, dbqkv = _dw_db(meta, dqkv, xn, wqkv, bqkv)
     if ln_w is None:                     # no LayerNorm: the projection's input gradient IS the result
         if residual:

@@ -7,6 +7,7 @@ arithmetic result comes from a kernel in libnrv_hip.so.  All tensors must live o
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import torch
@@ -408,7 +409,7 @@ def attn_sinkhorn_bwd(qkv: Tensor, dout: Tensor, lse: Tensor, scal: Tensor, B: i
     return dqkv
 
 
-# ---- batched strided GEMM + the composed robust attention -----------------------------------------------------------------
+# ---- batched strided GEMM + attention composed on the materialised matrix -------------------------------------------------
 def bgemm(A, a_str, B_, b_str, C, c_str, G1: int, G2: int, M: int, N: int, K: int, alpha: float = 1.0) -> None:
     """C[g1,g2] = alpha * A[g1,g2] . B[g1,g2] (include/nrv.h nrv_bgemm).  A, B, C: (tensor, element offset) pairs; *_str =
     (row stride, column stride, g1 stride, g2 stride) in elements.  The tensors are only memory: the strides do the addressing,
@@ -427,65 +428,108 @@ def bgemm(A, a_str, B_, b_str, C, c_str, G1: int, G2: int, M: int, N: int, K: in
          "nrv_bgemm")
 
 
-def _head_strides(H: int, dh: int, width: int, N: int):
-    """(row, col, batch, head) element strides of one head's [N, dh] slice inside a [B*N, width] projection."""
-    return (width, 1, N * width, dh)
-
-
-def _sinkhorn_scores(qkv: Tensor, B: int, N: int, H: int, dh: int, scale: float) -> Tensor:
-    """S[b,h] = scale * q k^T, fp32 [B,H,N,N] (simple_vit.py:70)."""
+def _composed_strides(N: int, H: int, dh: int):
+    """(row, col, batch, head) element strides of one head's [N, dh] slice of q, k or v inside qkv [B*N, 3*H*dh] (and read
+    transposed), of one head's slice of out / dout [B*N, H*dh], and of one head's [N, N] block of a [B,H,N,N] matrix (and transposed)."""
     W = 3 * H * dh
-    rs, cs, bs, hs = _head_strides(H, dh, W, N)
+    return (W, 1, N * W, dh), (1, W, N * W, dh), (H * dh, 1, N * H * dh, dh), (N, 1, H * N * N, N * N), (1, N, H * N * N, N * N)
+
+
+@dataclass
+class ComposedSaved:
+    """What attn_composed_bwd needs from attn_composed_fwd: P, the matrix that met v (None: the backward recomputes it), the
+    Sinkhorn op's statistics (lse [B*H, N], avec, bvec) and the call's keep mask, its scale, the iteration count and the bias."""
+    P: Optional[Tensor]
+    lse: Tensor
+    avec: Tensor
+    bvec: Tensor
+    keep: Optional[Tensor]
+    pscale: float
+    iters: int
+    bias: Optional[Tensor]
+
+
+def _composed_scores(qkv: Tensor, B: int, N: int, H: int, dh: int, scale: float, bias: Optional[Tensor]) -> Tensor:
+    """S[b,h] = scale * q k^T (+ bias), fp32 [B,H,N,N] (simple_vit.py:70)."""
+    hq, hqT, _, mat, _ = _composed_strides(N, H, dh)
     S = torch.empty(B, H, N, N, dtype=torch.float32, device=qkv.device)
-    bgemm((qkv, 0), (rs, cs, bs, hs), (qkv, H * dh), (cs, rs, bs, hs), (S, 0), (N, 1, H * N * N, N * N), B, H, N, N, dh, scale)
+    bgemm((qkv, 0), hq, (qkv, H * dh), hqT, (S, 0), mat, B, H, N, N, dh, scale)
+    if bias is not None:
+        _f32(bias, "bias")
+        S += bias                                   # broadcast over batch / heads: plumbing, once per call (not a BASELINE path)
     return S
 
 
-def _attn_sinkhorn_fwd_composed(qkv: Tensor, B: int, N: int, H: int, dh: int, scale: float, saved: Optional[dict] = None):
-    W = 3 * H * dh
-    rs, cs, bs, hs = _head_strides(H, dh, W, N)
-    S = _sinkhorn_scores(qkv, B, N, H, dh, scale)
-    P, lse, avec, bvec = sinkhorn_fwd(S, iters=3)                 # SinkhornAttention on the materialised scores (utils.py:1031-1037)
+def _composed_probs(S: Tensor, iters: int, keep: Optional[Tensor], pscale: float):
+    """(P, lse, avec, bvec): the Sinkhorn op on the scores (utils.py:1031-1037; 0 iterations = softmax), then the keep mask."""
+    P, lse, avec, bvec = sinkhorn_fwd(S, iters=iters)
+    if keep is not None:
+        mask_mul_f32(P, keep, pscale, out=P)
+    return P, lse, avec, bvec
+
+
+def attn_composed_fwd(qkv: Tensor, B: int, N: int, H: int, dh: int, scale: float, iters: int, keep: Optional[Tensor] = None,
+                      pscale: float = 1.0, bias: Optional[Tensor] = None):
+    """Attention on the materialised [B,H,N,N] matrix, for what the fused kernels do not take: robust=True beyond their shapes
+    (iters = 3), dropout on the attention weights (vit.py:108; `keep` uint8 [B,H,N,N], kept weights times `pscale`) and an additive
+    score bias (masks of torch's MultiheadAttention, utils.py:741-751: fp32, broadcast to [B,H,N,N], -inf = masked).  Scores (+ bias),
+    the Sinkhorn op (iters = 0: softmax), the keep mask, P v -- the reference's own structure.  Returns (out bf16, ComposedSaved)."""
+    _bf16(qkv, "qkv")
+    if keep is not None and tuple(keep.shape) != (B, H, N, N):
+        raise NrvError(f"attn_composed_fwd: keep must be a uint8 mask of shape {(B, H, N, N)}")
+    hq, _, ho, mat, _ = _composed_strides(N, H, dh)
+    S = _composed_scores(qkv, B, N, H, dh, scale, bias)
+    P, lse, avec, bvec = _composed_probs(S, iters, keep, pscale)
     del S
     out = torch.empty(B * N, H * dh, dtype=torch.bfloat16, device=qkv.device)
-    ors, ocs, obs, ohs = _head_strides(H, dh, H * dh, N)
-    # O[b,h] = P7 v   (attn v, simple_vit.py:74; P7 enters the product in bf16 as in the fused kernels)
-    bgemm((P, 0), (N, 1, H * N * N, N * N), (qkv, 2 * H * dh), (rs, cs, bs, hs), (out, 0), (ors, ocs, obs, ohs), B, H, N, dh, N, 1.0)
+    # O[b,h] = P v   (attn v, simple_vit.py:74; P enters the product in bf16 as in the fused kernels)
+    bgemm((P, 0), mat, (qkv, 2 * H * dh), hq, (out, 0), ho, B, H, N, dh, N, 1.0)
+    return out, ComposedSaved(P, lse, avec, bvec, keep, pscale, iters, bias)
+
+
+def attn_composed_bwd(qkv: Tensor, dout: Tensor, saved: ComposedSaved, B: int, N: int, H: int, dh: int, scale: float) -> Tensor:
+    """dqkv of attn_composed_fwd.  Takes P out of `saved` (freed once its two products are done); without it (the robust path did
+    not keep it, or a second backward) P is recomputed from the scores the Sinkhorn backward needs anyway."""
+    hq, hqT, ho, mat, matT = _composed_strides(N, H, dh)
+    S = _composed_scores(qkv, B, N, H, dh, scale, saved.bias)      # masked scores are -inf: P0 = 0 there, and so is dS
+    P, saved.P = saved.P, None
+    if P is None:
+        P = _composed_probs(S, saved.iters, saved.keep, saved.pscale)[0]
+    dqkv = torch.empty_like(qkv)
+    # dV = P^T dO
+    bgemm((P, 0), matT, (dout, 0), ho, (dqkv, 2 * H * dh), hq, B, H, N, dh, N, 1.0)
+    # dP = dO v^T, reusing P's storage would alias an operand of nothing that follows: a buffer of its own keeps it simple
+    dP = torch.empty_like(P)
+    bgemm((dout, 0), ho, (qkv, 2 * H * dh), hqT, (dP, 0), mat, B, H, N, N, dh, 1.0)
+    del P
+    if saved.keep is not None:
+        mask_mul_f32(dP, saved.keep, saved.pscale, out=dP)
+    dS = sinkhorn_bwd(S, dP, saved.lse, saved.avec, saved.bvec, iters=saved.iters)
+    del dP, S
+    # dQ = scale dS k ;  dK = scale dS^T q
+    bgemm((dS, 0), mat, (qkv, H * dh), hq, (dqkv, 0), hq, B, H, N, dh, N, scale)
+    bgemm((dS, 0), matT, (qkv, 0), hq, (dqkv, H * dh), hq, B, H, N, dh, N, scale)
+    return dqkv
+
+
+def _attn_sinkhorn_fwd_composed(qkv: Tensor, B: int, N: int, H: int, dh: int, scale: float, saved: Optional[dict] = None):
+    out, cs = attn_composed_fwd(qkv, B, N, H, dh, scale, iters=3)
     # the model keeps ONE form of the saved statistics: [B,H,7,N] = a1 b1 a2 b2 a3 b3 a4 (cumulative), as the fused kernel writes it
     scal = torch.empty(B, H, 7, N, dtype=torch.float32, device=qkv.device)
-    scal[:, :, 0::2] = avec.reshape(B, H, 4, N)
-    scal[:, :, 1::2] = bvec.reshape(B, H, 3, N)
-    if saved is not None and P.numel() * 4 <= SINKHORN_KEEP_P_BYTES:
-        saved["P7"] = P
-    return out, lse.reshape(B, H, N), scal
+    scal[:, :, 0::2] = cs.avec.reshape(B, H, 4, N)
+    scal[:, :, 1::2] = cs.bvec.reshape(B, H, 3, N)
+    if saved is not None and cs.P.numel() * 4 <= SINKHORN_KEEP_P_BYTES:
+        saved["P7"] = cs.P
+    return out, cs.lse.reshape(B, H, N), scal
 
 
 def _attn_sinkhorn_bwd_composed(qkv: Tensor, dout: Tensor, lse: Tensor, scal: Tensor, B: int, N: int, H: int, dh: int, scale: float,
                                 saved: Optional[dict] = None) -> Tensor:
-    W = 3 * H * dh
-    rs, cs, bs, hs = _head_strides(H, dh, W, N)
-    ors, ocs, obs, ohs = _head_strides(H, dh, H * dh, N)
-    mat = (N, 1, H * N * N, N * N)                                 # a [B,H,N,N] fp32 matrix
-    matT = (1, N, H * N * N, N * N)                                # ... read transposed
-    S = _sinkhorn_scores(qkv, B, N, H, dh, scale)                  # recomputed (one GEMM): the Sinkhorn backward rebuilds P0 from it
-    P = saved.pop("P7", None) if saved is not None else None       # the forward's matrix when it was small enough to keep
-    if P is None:
-        P, _, _, _ = sinkhorn_fwd(S, iters=3)
-    avec = scal[:, :, 0::2].reshape(B * H, 4, N).contiguous()
-    bvec = scal[:, :, 1::2].reshape(B * H, 3, N).contiguous()
-    dqkv = torch.empty_like(qkv)
-    # dV = P7^T dO
-    bgemm((P, 0), matT, (dout, 0), (ors, ocs, obs, ohs), (dqkv, 2 * H * dh), (rs, cs, bs, hs), B, H, N, dh, N, 1.0)
-    # dP7 = dO v^T, reusing P's storage would alias an operand of nothing that follows: a buffer of its own keeps it simple
-    dP = torch.empty_like(P)
-    bgemm((dout, 0), (ors, ocs, obs, ohs), (qkv, 2 * H * dh), (cs, rs, bs, hs), (dP, 0), mat, B, H, N, N, dh, 1.0)
-    del P
-    dS = sinkhorn_bwd(S, dP, lse.reshape(B * H, N).contiguous(), avec, bvec, iters=3)
-    del dP, S
-    # dQ = scale dS k ;  dK = scale dS^T q
-    bgemm((dS, 0), mat, (qkv, H * dh), (rs, cs, bs, hs), (dqkv, 0), (rs, cs, bs, hs), B, H, N, dh, N, scale)
-    bgemm((dS, 0), matT, (qkv, 0), (rs, cs, bs, hs), (dqkv, H * dh), (rs, cs, bs, hs), B, H, N, dh, N, scale)
-    return dqkv
+    # P7 goes straight into the record (no local name here), so the backward frees it as soon as it is used
+    cs = ComposedSaved(saved.pop("P7", None) if saved is not None else None, lse.reshape(B * H, N).contiguous(),
+                       scal[:, :, 0::2].reshape(B * H, 4, N).contiguous(), scal[:, :, 1::2].reshape(B * H, 3, N).contiguous(),
+                       keep=None, pscale=1.0, iters=3, bias=None)
+    return attn_composed_bwd(qkv, dout, cs, B, N, H, dh, scale)
 
 
 def patch_unfold(img: Tensor, p: int, layout: int) -> Tensor:
@@ -577,55 +621,6 @@ def mask_mul_f32(a: Tensor, keep: Tensor, scale: float, out: Optional[Tensor] = 
     _run("dropout", 0.0, a.numel() * 9,
          lambda: lib.nrv_mask_mul_f32(a.data_ptr(), keep.data_ptr(), o.data_ptr(), float(scale), a.numel(), _stream()), "nrv_mask_mul_f32")
     return o
-
-
-def attn_dropout_fwd(qkv: Tensor, B: int, N: int, H: int, dh: int, scale: float, robust: bool, keep: Optional[Tensor], pscale: float,
-                     bias: Optional[Tensor] = None):
-    """Attention with what the fused kernels do not take, composed on the materialised matrix like the robust attention beyond the
-    fused shapes: an additive score bias (attention / key-padding masks of torch's MultiheadAttention: utils.py:741-751; -inf = masked)
-    and / or dropout ON THE ATTENTION WEIGHTS (attention_dropout > 0: vit.py:108) -- scores (+ bias), softmax (the Sinkhorn op with
-    0 iterations) or the Sinkhorn normalisation (robust), the keep mask [B,H,N,N], P v.  Returns (out bf16, saved) with what the
-    backward needs (the matrix that met v, the statistics)."""
-    _bf16(qkv, "qkv")
-    W = 3 * H * dh
-    rs, cs, bs, hs = _head_strides(H, dh, W, N)
-    iters = 3 if robust else 0
-    S = _sinkhorn_scores(qkv, B, N, H, dh, scale)
-    if bias is not None:
-        _f32(bias, "bias")
-        S += bias                                   # broadcast over batch / heads: plumbing, once per call (not a BASELINE path)
-    P, lse, avec, bvec = sinkhorn_fwd(S, iters=iters)
-    del S
-    if keep is not None:
-        if tuple(keep.shape) != (B, H, N, N):
-            raise NrvError(f"attn_dropout_fwd: keep must be a uint8 mask of shape {(B, H, N, N)}")
-        mask_mul_f32(P, keep, pscale, out=P)
-    out = torch.empty(B * N, H * dh, dtype=torch.bfloat16, device=qkv.device)
-    ors, ocs, obs, ohs = _head_strides(H, dh, H * dh, N)
-    bgemm((P, 0), (N, 1, H * N * N, N * N), (qkv, 2 * H * dh), (rs, cs, bs, hs), (out, 0), (ors, ocs, obs, ohs), B, H, N, dh, N, 1.0)
-    return out, (P, lse, avec, bvec, keep, pscale, iters, bias)
-
-
-def attn_dropout_bwd(qkv: Tensor, dout: Tensor, saved, B: int, N: int, H: int, dh: int, scale: float) -> Tensor:
-    Pd, lse, avec, bvec, keep, pscale, iters, bias = saved
-    W = 3 * H * dh
-    rs, cs, bs, hs = _head_strides(H, dh, W, N)
-    ors, ocs, obs, ohs = _head_strides(H, dh, H * dh, N)
-    mat, matT = (N, 1, H * N * N, N * N), (1, N, H * N * N, N * N)
-    dqkv = torch.empty_like(qkv)
-    bgemm((Pd, 0), matT, (dout, 0), (ors, ocs, obs, ohs), (dqkv, 2 * H * dh), (rs, cs, bs, hs), B, H, N, dh, N, 1.0)          # dV = Pd^T dO
-    dP = torch.empty_like(Pd)
-    bgemm((dout, 0), (ors, ocs, obs, ohs), (qkv, 2 * H * dh), (cs, rs, bs, hs), (dP, 0), mat, B, H, N, N, dh, 1.0)           # d(Pd) = dO v^T
-    if keep is not None:
-        mask_mul_f32(dP, keep, pscale, out=dP)                                                                                  # dP
-    S = _sinkhorn_scores(qkv, B, N, H, dh, scale)
-    if bias is not None:
-        S += bias                                   # masked scores are -inf: P0 = 0 there, and so is dS
-    dS = sinkhorn_bwd(S, dP, lse, avec, bvec, iters=iters)
-    del dP, S
-    bgemm((dS, 0), mat, (qkv, H * dh), (rs, cs, bs, hs), (dqkv, 0), (rs, cs, bs, hs), B, H, N, dh, N, scale)
-    bgemm((dS, 0), matT, (qkv, 0), (rs, cs, bs, hs), (dqkv, H * dh), (rs, cs, bs, hs), B, H, N, dh, N, scale)
-    return dqkv
 
 
 def gather_rows(src: Tensor, index: Tensor) -> Tensor:

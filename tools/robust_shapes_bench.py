@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Step time of robust=True (Sinkhorn attention) models at the shapes the fused kernels do not take -- the composed path (nrv_bgemm +
-SinkhornAttention on materialised scores, kernels._attn_sinkhorn_*_composed) -- next to the same models with softmax attention
+SinkhornAttention on materialised scores, kernels.attn_composed_fwd/bwd) -- next to the same models with softmax attention
 (streaming kernels) and to the fused Sinkhorn kernels at 224 px.  GPU only; dev tool."""
 import os
 import sys

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NRV_ABI_VERSION 13
+#define NRV_ABI_VERSION 14
 
 /* dtype codes */
 #define NRV_F32 0
@@ -188,6 +188,29 @@ int nrv_attn_bwd(const void* qkv_bf16, const void* out_bf16, const void* dout_bf
  *   probs fp32 [B, H, N, N] = exp(scale * q.k - lse), i.e. the softmax the fused kernels keep on chip. */
 int nrv_attn_probs(const void* qkv_bf16, const float* lse, float* probs,
                    int B, int N, int H, int dh, float scale, int layout, void* stream);
+
+/* Attention with memory keys and a score mask (ABI 14; learnable_memory_vit.py:64-86, the Adapter's attention).
+ *   Queries: the Nq token rows of qkv bf16 [B, Nq, 3*H*dh] (same layout as nrv_attn_fwd).  Keys / values: those Nq rows
+ *   followed by M memory rows, Nk = Nq + M; memory row r of sample b is row b*mem_bstride + r of mem_kv bf16 [*, 2*H*dh]
+ *   (k features h*dh + d, v features H*dh + h*dh + d); mem_bstride = 0 (one set for every sample) or M (one set per sample).
+ *   mask (optional, NULL = every pair): bit (key & 31) of the 32-bit word b*mask_bstride + h*mask_hstride + q*W + (key >> 5),
+ *   W = ceil(Nk / 32), 1 = may attend; strides in words, 0 = broadcast.  A masked score is -FLT_MAX (masked_fill of the
+ *   reference), so a query whose keys are all masked gets uniform weights over the Nk keys; its lse is written as -FLT_MAX.
+ *   dh in {32, 64, 80, 96, 128}, any Nq >= 1, M >= 0; out bf16 [B, Nq, H*dh]; lse fp32 [B, H, Nq] (natural log).
+ *   Backward: dqkv bf16 [B, Nq, 3*H*dh] (token rows); dmem fp32 [B*M, 2*H*dh] per-sample gradient of the memory rows' k / v;
+ *   dmem_sum (optional, shared memories only) fp32 [M, 2*H*dh] = that gradient summed over the batch in a fixed order (groups
+ *   of 16 samples, then the groups); dmem is then its scratch and holds partial sums afterwards.
+ *   delta_ws fp32 [B*H*Nq] scratch.  Deterministic (no atomics). */
+int nrv_attn_mem_fwd(const void* qkv_bf16, const void* mem_kv_bf16, int64_t mem_bstride, int M,
+                     const uint32_t* mask, int64_t mask_bstride, int64_t mask_hstride,
+                     void* out_bf16, float* lse, int B, int Nq, int H, int dh, float scale, void* stream);
+int nrv_attn_mem_bwd(const void* qkv_bf16, const void* out_bf16, const void* dout_bf16, const float* lse,
+                     const void* mem_kv_bf16, int64_t mem_bstride, int M,
+                     const uint32_t* mask, int64_t mask_bstride, int64_t mask_hstride,
+                     void* dqkv_bf16, float* dmem_f32, float* dmem_sum_f32, float* delta_ws,
+                     int B, int Nq, int H, int dh, float scale, void* stream);
+/* bool / uint8 [rows, cols] (non-zero = 1) -> the bit words above: uint32 [rows, ceil(cols / 32)] */
+int nrv_mask_pack_bits(const void* mask_u8, uint32_t* bits, int64_t rows, int cols, void* stream);
 
 /* "robust" attention (robust=True): softmax followed by Sinkhorn normalisation -- 3 x (row /, column /) and a final
  * row / -- utils.py:1025-1037, wired at simple_vit.py:56-57.  Same layouts as nrv_attn_fwd.

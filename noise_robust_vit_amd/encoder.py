@@ -223,9 +223,16 @@ def _queue(meta: BlockMeta, q: dict) -> None:
         wgrad_flush(meta)
 
 
-def _dw_db(meta: BlockMeta, dy16: Tensor, x16: Tensor, w: Tensor, b: Optional[Tensor]):
+def _dw_db(meta: BlockMeta, dy16: Tensor, x16: Tensor, w: Tensor, b: Optional[Tensor], need=None):
     """Queue the weight and bias gradient of y = x W^T + b (dW = dy^T x on the MFMA, db = colsum(dy) fused into the same kernel).
-    Returns (dW, db) as the tensors the launch of `wgrad_flush` will fill: the sink's flat-buffer views, or fresh ones."""
+    Returns (dW, db) as the tensors the launch of `wgrad_flush` will fill: the sink's flat-buffer views, or fresh ones.
+    `need` (optional (dW wanted, db wanted)): nothing is queued when neither is wanted (a frozen layer), the bias is left out
+    when only dW is."""
+    if need is not None:
+        if not need[0] and not need[1]:
+            return None, None
+        if not need[1]:
+            b = None
     parts = getattr(w, "_nrv_parts", None)
     if parts is not None and meta.sink is not None:
         # w stacks the rows of several parameters ([to_q; to_kv]): straight into their slots of the sink -- one problem when the
@@ -337,9 +344,20 @@ def draw_keep(meta: BlockMeta, site: int, shape, device, p: Optional[float] = No
     return (torch.rand(shape, device=device) >= (meta.dropout if p is None else p)).to(torch.uint8)
 
 
-def attn_half_fwd(x: Tensor, B: int, N: int, meta: BlockMeta, ln_w, ln_b, wqkv, bqkv, wo, bo, residual: bool, drop=None, adrop=None):
+class MemKV(NamedTuple):
+    """Memory keys / values and score mask of one attention layer (learnable_memory_vit.py:64-86): `rows` fp32 [M, D] (one set
+    for every sample) or [B*M, D] (one set per sample), None when M == 0; they skip the LayerNorm and go through to_kv only."""
+    rows: Optional[Tensor]
+    M: int
+    shared: bool
+    mask: Optional[K.MaskBits]
+
+
+def attn_half_fwd(x: Tensor, B: int, N: int, meta: BlockMeta, ln_w, ln_b, wqkv, bqkv, wo, bo, residual: bool, drop=None, adrop=None,
+                  mem: Optional[MemKV] = None):
     """x fp32 [B*N, D] -> (y fp32 [B*N, D], saved).  `ln_w is None`: no LayerNorm in front of the projection (the bare
-    `MultiheadAttention.forward` of the reference's forked module, utils.py:741-751)."""
+    `MultiheadAttention.forward` of the reference's forked module, utils.py:741-751).  `mem`: memory keys and / or a score
+    mask (nrv_attn_mem_*); wqkv is then the bias-free [to_q; to_kv] projection."""
     H, dh = meta.heads, meta.dim_head
     if ln_w is None:
         xn, mean, rstd = K.cast_bf16(x), None, None
@@ -350,7 +368,19 @@ def attn_half_fwd(x: Tensor, B: int, N: int, meta: BlockMeta, ln_w, ln_b, wqkv, 
     qkv = K.gemm_nt(xn, wqkv_b, out_dtype=torch.bfloat16,
                     epilogue=EPI_BIAS if bqkv is not None else EPI_NONE, bias=bqkv)
     scale = dh ** -0.5
-    if adrop is not None or meta.attn_bias is not None:      # weight dropout / score masks: the composed path (materialised matrix), softmax or Sinkhorn
+    if mem is not None:
+        if bqkv is not None or adrop is not None or meta.attn_bias is not None or meta.robust:
+            raise NrvError("memory keys / score masks go with a bias-free projection, plain softmax and no attention dropout")
+        if _RECORDING is not None:
+            raise NotImplementedError("recording attention maps is not supported with memory keys / score masks")
+        mem16 = mkv = None
+        if mem.M > 0:
+            # memories skip the LayerNorm and to_q: their k / v are the to_kv rows of the cached bf16 [to_q; to_kv] image
+            mem16 = K.cast_bf16(mem.rows)
+            mkv = K.gemm_nt(mem16, wqkv_b[H * dh:], out_dtype=torch.bfloat16)
+        o, lse = K.attn_mem_fwd(qkv, mkv, B, N, mem.M, H, dh, scale, mem.shared, mem.mask)
+        att = AttnSaved("memory", lse, saved=(mem, mem16, mkv))
+    elif adrop is not None or meta.attn_bias is not None:      # weight dropout / score masks: the composed path (materialised matrix), softmax or Sinkhorn
         pscale, akeep = 1.0, None
         if adrop is not None:
             pscale, asite, pa = adrop
@@ -364,7 +394,7 @@ def attn_half_fwd(x: Tensor, B: int, N: int, meta: BlockMeta, ln_w, ln_b, wqkv, 
     else:
         o, lse = K.attn_fwd(qkv, B, N, H, dh, scale)
         att = AttnSaved("softmax", lse)
-    if _RECORDING is not None and att.kind != "composed":
+    if _RECORDING is not None and att.kind not in ("composed", "memory"):
         _record(qkv, att, B, N, H, dh, scale)
     keep = None
     if residual and drop is not None:
@@ -385,10 +415,14 @@ def attn_half_fwd(x: Tensor, B: int, N: int, meta: BlockMeta, ln_w, ln_b, wqkv, 
 
 
 def attn_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, B: int, N: int, meta: BlockMeta,
-                  ln_w, ln_b, wqkv, bqkv, wo, bo, residual: bool, want_bf16: bool, want_f32: bool = True, drop_scale: float = 1.0):
+                  ln_w, ln_b, wqkv, bqkv, wo, bo, residual: bool, want_bf16: bool, want_f32: bool = True, drop_scale: float = 1.0,
+                  need=None, mem_grad: Optional[list] = None):
     """Returns (dx32|None, dx16|None, [d ln_w, d ln_b, d wqkv, d bqkv, d wo, d bo]).
 
-    The incoming gradient is given as fp32 (`dy32`), bf16 (`dy16`) or both; the residual add uses fp32 when present."""
+    The incoming gradient is given as fp32 (`dy32`), bf16 (`dy16`) or both; the residual add uses fp32 when present.
+    `need` (optional, one flag per parameter): weight-gradient GEMMs of parameters without a flag are not issued.  With memory
+    keys, `mem_grad` (a list) receives the fp32 gradient of the memory rows (None when M == 0); the memory rows' share of
+    d wqkv is added to its to_kv rows."""
     x, xn, mean, rstd, qkv, o, att, keep = saved
     H, dh = meta.heads, meta.dim_head
     if dy16 is None:
@@ -398,16 +432,32 @@ def attn_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, B: int,
     _, wo_t = WEIGHTS.get(wo, True)
     _, wqkv_t = WEIGHTS.get(wqkv, True)
     # out-proj:  y = o Wo^T (+bo) (+x)
-    dwo, dbo = _dw_db(meta, dy16, o, wo, bo)
+    dwo, dbo = _dw_db(meta, dy16, o, wo, bo, None if need is None else need[4:6])
     do = K.gemm_nt(dy16, wo_t, out_dtype=torch.bfloat16)
     scale = dh ** -0.5
-    if att.kind == "composed":
+    dmkv = None
+    if att.kind == "memory":
+        mem, mem16, mkv = att.saved
+        dqkv, dmkv = K.attn_mem_bwd(qkv, o, do, att.lse, mkv, B, N, mem.M, H, dh, scale, mem.shared, mem.mask)
+    elif att.kind == "composed":
         dqkv = K.attn_composed_bwd(qkv, do, att.saved, B, N, H, dh, scale)
     elif att.kind == "sinkhorn":
         dqkv = K.attn_sinkhorn_bwd(qkv, do, att.lse, att.scal, B, N, H, dh, scale, saved=att.saved)
     else:
         dqkv = K.attn_bwd(qkv, o, do, att.lse, B, N, H, dh, scale)
-    dwqkv, dbqkv = _dw_db(meta, dqkv, xn, wqkv, bqkv)
+    dwqkv, dbqkv = _dw_db(meta, dqkv, xn, wqkv, bqkv, None if need is None else need[2:4])
+    if att.kind == "memory":
+        dmem = None
+        if dmkv is not None:
+            # dmem = dKV_mem Wkv; dWkv += dKV_mem^T mem (summed over the batch already for shared memories)
+            inner = H * dh
+            dmkv16 = K.cast_bf16(dmkv)
+            dmem = K.gemm_nt(dmkv16, wqkv_t[:, inner:], out_dtype=torch.float32)
+            if dwqkv is not None:
+                wgrad_flush(meta)                # the token rows' launch writes dwqkv first
+                K.gemm_tn(dmkv16, mem16, out=dwqkv[inner:], beta=1.0)
+        if mem_grad is not None:
+            mem_grad.append(dmem)
     if ln_w is None:                     # no LayerNorm: the projection's input gradient IS the result
         if residual:
             raise NrvError("a residual attention half needs its LayerNorm")
@@ -463,7 +513,8 @@ def mlp_half_fwd(x: Tensor, meta: BlockMeta, ln_w, ln_b, w1, b1, w2, b2, residua
 
 
 def mlp_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, meta: BlockMeta,
-                 ln_w, ln_b, w1, b1, w2, b2, residual: bool, want_bf16: bool, want_f32: bool = True, drop_scale: float = 1.0):
+                 ln_w, ln_b, w1, b1, w2, b2, residual: bool, want_bf16: bool, want_f32: bool = True, drop_scale: float = 1.0,
+                 need=None):
     x, xn, mean, rstd, u, h, keep2 = saved
     if dy16 is None:
         dy16 = K.cast_bf16(dy32)
@@ -473,9 +524,9 @@ def mlp_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, meta: Bl
         dy16 = K.mask_mul(dy16, keep2, drop_scale)
     _, w2_t = WEIGHTS.get(w2, True)
     _, w1_t = WEIGHTS.get(w1, True)
-    dw2, db2 = _dw_db(meta, dy16, h, w2, b2)
+    dw2, db2 = _dw_db(meta, dy16, h, w2, b2, None if need is None else need[4:6])
     du = K.gemm_nt(dy16, w2_t, out_dtype=torch.bfloat16, epilogue=EPI_DGELU_Q8 if u.dtype == torch.uint8 else EPI_DGELU, aux=u)
-    dw1, db1 = _dw_db(meta, du, xn, w1, b1)
+    dw1, db1 = _dw_db(meta, du, xn, w1, b1, None if need is None else need[2:4])
     dxn = K.gemm_nt(du, w1_t, out_dtype=torch.bfloat16)
     tg, bg = _grad_target(meta, ln_w)
     tb, _ = _grad_target(meta, ln_b)
@@ -590,6 +641,117 @@ class AttnHalfFn(torch.autograd.Function):
         dx32, _, g = attn_half_bwd(d32, None, ctx.saved_half, B, N, ctx.meta, *ctx.params, residual=False, want_bf16=False,
                                    drop_scale=ctx.drop_scale)
         return (dx32.reshape(B, N, D), None, *_mask_sink_grads(ctx.meta, g))
+
+
+# ----------------------------------------------------------------------------------------------
+# memory keys and score masks (learnable_memory_vit.py:64-102, the Adapter)
+# ----------------------------------------------------------------------------------------------
+class MaskCache:
+    """bool mask -> packed bits (kernels.mask_pack), reused while the tensor is alive and unchanged: keyed on (data_ptr, version,
+    shape) and the attention's geometry, like WeightCache (the Adapter's `attn_mask` buffer is packed once)."""
+
+    def __init__(self, size: int = 16) -> None:
+        self._d = {}
+        self.size = size
+
+    def get(self, mask: Tensor, B: int, H: int, Nq: int, Nk: int) -> K.MaskBits:
+        key = (mask.data_ptr(), tuple(mask.shape), tuple(mask.stride()), B, H, Nq, Nk)
+        ent = self._d.get(key)
+        if ent is not None and ent[0]() is mask and ent[1] == mask._version:
+            return ent[2]
+        bits = K.mask_pack(mask, B, H, Nq, Nk)
+        if len(self._d) >= self.size:
+            self._d = {k: v for k, v in self._d.items() if v[0]() is not None}
+            if len(self._d) >= self.size:
+                self._d.clear()
+        self._d[key] = (weakref.ref(mask), mask._version, bits)
+        return bits
+
+
+MASKS = MaskCache()
+
+
+def _mem_kv(m: Optional[Tensor], B: int, D: int, M: int, mask: Optional[K.MaskBits]) -> MemKV:
+    if m is None:
+        return MemKV(None, 0, True, mask)
+    if m.dim() not in (2, 3) or m.shape[-1] != D or m.shape[-2] != M or (m.dim() == 3 and m.shape[0] != B):
+        raise NrvError(f"memories must be [M, {D}] or [{B}, M, {D}] with the same M in every layer, got {tuple(m.shape)}")
+    if not m.is_cuda:
+        raise NrvError("memories must be on the MI355X (HIP) device")
+    rows = m.detach().to(torch.float32).contiguous().reshape(-1, D) if M > 0 else None
+    return MemKV(rows, M, m.dim() == 2, mask)
+
+
+class MemStackFn(torch.autograd.Function):
+    """The encoder stack (EncoderStackFn) or one stand-alone attention (AttnHalfFn, `attn_only`) with memory keys and / or a
+    score mask in every attention (learnable_memory_vit.py:64-102).  Inputs: x, meta, attn_only, packed mask (or None), the
+    number of memory tensors (depth, or 0), those tensors ([M, D] shared / [B, M, D] per sample, one per layer), then
+    PARAMS_PER_LAYER parameters per layer (6 with attn_only).  No dropout, no gradient sink.
+
+    The backward returns gradients for the memories and issues no weight-gradient GEMM for a parameter that does not require
+    one (the Adapter's frozen backbone): the flags come from autograd's needs_input_grad."""
+
+    @staticmethod
+    def forward(ctx, x, meta: BlockMeta, attn_only: bool, mask: Optional[K.MaskBits], n_mem: int, *rest):
+        if meta.sink is not None:
+            raise NotImplementedError("memory keys / score masks are not wired to a gradient sink (data-parallel runtime)")
+        if meta.dropout > 0.0 or meta.attn_dropout > 0.0:
+            raise NotImplementedError("dropout together with memory keys / score masks is not implemented")
+        x2, B, N, D = _as_stream(x)
+        _PENDING.clear()
+        mems, params = rest[:n_mem], rest[n_mem:]
+        per = 6 if attn_only else PARAMS_PER_LAYER
+        depth = len(params) // per
+        if n_mem and n_mem != depth:
+            raise NrvError(f"{n_mem} memory tensors for {depth} layers")
+        M = mems[0].shape[-2] if n_mem else 0
+        if mask is not None and (mask.Nq != N or mask.Nk != N + M):
+            raise NrvError(f"mask packed for [{mask.Nq}, {mask.Nk}], attention is [{N}, {N + M}]")
+        train = any(ctx.needs_input_grad)
+        saved, cur = [], x2
+        for i in range(depth):
+            p = params[i * per:(i + 1) * per]
+            mk = _mem_kv(mems[i] if n_mem else None, B, D, M, mask)
+            cur, sa = attn_half_fwd(cur, B, N, meta, *p[0:6], residual=not attn_only, mem=mk)
+            sm = None
+            if not attn_only:
+                cur, sm = mlp_half_fwd(cur, meta, *p[6:12], residual=True, save=train)
+            saved.append((sa, sm) if train else None)
+        ctx.meta, ctx.params, ctx.saved_blocks, ctx.shape = meta, params, saved, (B, N, D)
+        ctx.attn_only, ctx.n_mem, ctx.mem_shapes = attn_only, n_mem, [tuple(m.shape) for m in mems]
+        return cur.reshape(B, N, -1)
+
+    @staticmethod
+    def backward(ctx, dy):
+        meta, params, saved = ctx.meta, ctx.params, ctx.saved_blocks
+        B, N, D = ctx.shape
+        attn_only, n_mem = ctx.attn_only, ctx.n_mem
+        per = 6 if attn_only else PARAMS_PER_LAYER
+        depth = len(params) // per
+        need_mem = ctx.needs_input_grad[5:5 + n_mem]
+        need_p = ctx.needs_input_grad[5 + n_mem:]
+        d32 = dy.to(torch.float32).contiguous().reshape(B * N, -1)
+        d16 = None
+        grads: List[Optional[Tensor]] = [None] * len(params)
+        mgrads: List[Optional[Tensor]] = [None] * n_mem
+        for i in reversed(range(depth)):
+            p = params[i * per:(i + 1) * per]
+            need = need_p[i * per:(i + 1) * per]
+            sa, sm = saved[i]
+            gm = []
+            if not attn_only:
+                d32, d16, gm = mlp_half_bwd(d32, d16, sm, meta, *p[6:12], residual=True, want_bf16=True, need=need[6:12])
+            mg: list = []
+            d32, d16, ga = attn_half_bwd(d32, d16, sa, B, N, meta, *p[0:6], residual=not attn_only, want_bf16=i > 0 and not attn_only,
+                                         need=need[0:6], mem_grad=mg)
+            wgrad_flush(meta)
+            g = ga + gm
+            grads[i * per:(i + 1) * per] = [t if f else None for t, f in zip(g, need)]
+            if n_mem and need_mem[i] and mg[0] is not None:
+                mgrads[i] = mg[0].reshape(ctx.mem_shapes[i])
+            saved[i] = None
+        wgrad_join()
+        return (d32.reshape(B, N, D), None, None, None, None, *mgrads, *grads)
 
 
 class MlpHalfFn(torch.autograd.Function):

@@ -362,6 +362,94 @@ def attn_probs(qkv: Tensor, lse: Tensor, B: int, N: int, H: int, dh: int, scale:
     return probs
 
 
+@dataclass
+class MaskBits:
+    """A boolean score mask packed for nrv_attn_mem_*: int32 words [*, ceil(Nk / 32)] per query row, with the batch / head
+    strides in words (0 = broadcast)."""
+    bits: Tensor
+    Nq: int
+    Nk: int
+    bstride: int
+    hstride: int
+
+
+def mask_pack(mask: Tensor, B: int, H: int, Nq: int, Nk: int) -> MaskBits:
+    """bool mask broadcastable to [B, H, Nq, Nk] (True = may attend) -> MaskBits, packed on the device (no host sync)."""
+    _dev(mask, "mask")
+    if mask.dtype != torch.bool:
+        raise NrvError(f"attention mask must be bool, got {mask.dtype}")
+    if mask.dim() > 4:
+        raise NrvError(f"attention mask of {mask.dim()} dims does not broadcast against [B, H, Nq, Nk]")
+    m = mask.reshape((1,) * (4 - mask.dim()) + tuple(mask.shape))
+    mb, mh = m.shape[0], m.shape[1]
+    if mb not in (1, B) or mh not in (1, H):
+        raise NrvError(f"attention mask {tuple(mask.shape)} does not broadcast against {(B, H, Nq, Nk)}")
+    try:
+        m = m.expand(mb, mh, Nq, Nk).contiguous()          # only the query / key dims are ever materialised
+    except RuntimeError as e:
+        raise NrvError(f"attention mask {tuple(mask.shape)} does not broadcast against {(B, H, Nq, Nk)}") from e
+    W = (Nk + 31) // 32
+    bits = torch.empty(mb * mh * Nq, W, dtype=torch.int32, device=mask.device)
+    check(_lib.load().nrv_mask_pack_bits(m.data_ptr(), bits.data_ptr(), mb * mh * Nq, Nk, _stream()), "nrv_mask_pack_bits")
+    return MaskBits(bits, Nq, Nk, mh * Nq * W if mb > 1 else 0, Nq * W if mh > 1 else 0)
+
+
+def _mem_args(mkv: Optional[Tensor], M: int, shared: bool, mask: Optional[MaskBits], Nq: int, H: int, dh: int):
+    if M > 0:
+        _bf16(mkv, "mem_kv")
+        rows, cols, ld = _rows2d(mkv, "mem_kv")
+        if cols != 2 * H * dh or ld != cols or rows < M:
+            raise NrvError(f"mem_kv must be contiguous [*, {2 * H * dh}] with at least {M} rows")
+    if mask is not None and (mask.Nq != Nq or mask.Nk != Nq + M):
+        raise NrvError(f"mask packed for [{mask.Nq}, {mask.Nk}], attention is [{Nq}, {Nq + M}]")
+    mptr = mkv.data_ptr() if M > 0 else None
+    kptr, bs, hs = (mask.bits.data_ptr(), mask.bstride, mask.hstride) if mask is not None else (None, 0, 0)
+    return mptr, 0 if shared else M, kptr, bs, hs
+
+
+def attn_mem_fwd(qkv: Tensor, mkv: Optional[Tensor], B: int, Nq: int, M: int, H: int, dh: int, scale: float,
+                 shared: bool = True, mask: Optional[MaskBits] = None):
+    """Softmax attention of the Nq token queries over Nq token keys + M memory keys (learnable_memory_vit.py:64-86).
+    qkv bf16 [B*Nq, 3*H*dh]; mkv bf16 [M, 2*H*dh] (shared) or [B*M, 2*H*dh] (per sample) -> (out bf16 [B*Nq, H*dh], lse fp32 [B,H,Nq])."""
+    _bf16(qkv, "qkv")
+    if not qkv.is_contiguous() or qkv.numel() != B * Nq * 3 * H * dh:
+        raise NrvError("attn_mem_fwd: qkv must be contiguous [B*Nq, 3*H*dh]")
+    if M > 0 and not shared and mkv is not None and mkv.shape[0] != B * M:
+        raise NrvError("attn_mem_fwd: per-sample memories need B*M rows")
+    mptr, mstride, kptr, bs, hs = _mem_args(mkv, M, shared, mask, Nq, H, dh)
+    out = torch.empty(B * Nq, H * dh, dtype=torch.bfloat16, device=qkv.device)
+    lse = torch.empty(B, H, Nq, dtype=torch.float32, device=qkv.device)
+    Nk = Nq + M
+    lib = _lib.load()
+    _run("attn_mem_fwd", 4.0 * B * H * Nq * Nk * dh, 2 * B * (2 * Nq + Nk) * H * dh * 2,
+         lambda: lib.nrv_attn_mem_fwd(qkv.data_ptr(), mptr, mstride, M, kptr, bs, hs, out.data_ptr(), lse.data_ptr(),
+                                      B, Nq, H, dh, float(scale), _stream()),
+         "nrv_attn_mem_fwd")
+    return out, lse
+
+
+def attn_mem_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, mkv: Optional[Tensor], B: int, Nq: int, M: int, H: int,
+                 dh: int, scale: float, shared: bool = True, mask: Optional[MaskBits] = None):
+    """-> (dqkv bf16 [B*Nq, 3*H*dh], dmem_kv fp32 [M, 2*H*dh] summed over the batch (shared) / [B*M, 2*H*dh] (per sample),
+    None when M == 0)."""
+    _bf16(qkv, "qkv"); _bf16(out, "out"); _bf16(dout, "dout"); _f32(lse, "lse")
+    if not (qkv.is_contiguous() and out.is_contiguous() and dout.is_contiguous() and lse.is_contiguous()):
+        raise NrvError("attn_mem_bwd: operands must be contiguous")
+    mptr, mstride, kptr, bs, hs = _mem_args(mkv, M, shared, mask, Nq, H, dh)
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty(B * H * Nq, dtype=torch.float32, device=qkv.device)
+    dmem = torch.empty(B * M, 2 * H * dh, dtype=torch.float32, device=qkv.device) if M > 0 else None
+    dsum = torch.empty(M, 2 * H * dh, dtype=torch.float32, device=qkv.device) if M > 0 and shared else None
+    Nk = Nq + M
+    lib = _lib.load()
+    _run("attn_mem_bwd", 10.0 * B * H * Nq * Nk * dh, 2 * B * (4 * Nq + 2 * Nk) * H * dh * 2,
+         lambda: lib.nrv_attn_mem_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), mptr, mstride, M,
+                                      kptr, bs, hs, dqkv.data_ptr(), _ptr(dmem), _ptr(dsum), delta.data_ptr(),
+                                      B, Nq, H, dh, float(scale), _stream()),
+         "nrv_attn_mem_bwd")
+    return dqkv, (dsum if dsum is not None else dmem)
+
+
 def _sinkhorn_fused_shape(N: int, dh: int) -> bool:
     """Shapes the fused kernels hold on chip (csrc/nrv_sinkhorn.hip): the head's whole [N, N] matrix in registers."""
     return dh == 64 and N <= 256

@@ -4,16 +4,22 @@ This is the encoder family the reference's `MAE` wrapper expects (`mae.py:29-31`
 `pos_embedding [1, n+1, d]`, `transformer`); module tree, constructor arguments and state_dict keys follow
 `/root/reference/vit_pytorch_robust/learnable_memory_vit.py:30-151` (FeedForward keys `net.0,1,4`; Attention keys
 `norm, to_q, to_kv, to_out.0`; `Transformer(dim, depth, heads, dim_head, mlp_dim, dropout)`; `ViT(...)`).
-Dropout arguments are accepted, p = 0 is what the fused path implements.  The adapter / memory arguments of the
-reference's `forward(x, attn_mask, memories)` are outside the hot path and must be None.
+Dropout arguments are accepted, p = 0 is what the fused path implements.
+
+`forward(x, attn_mask, memories)` of `Attention` / `Transformer` and the `Adapter` (learnable_memory_vit.py:64-102,155-205:
+fine-tuning a frozen ViT through learnable memory tokens) run the memory / mask attention kernels (nrv_attn_mem_*) inside
+encoder.MemStackFn: `attn_mask` bool, True = may attend, broadcastable to [B, H, Nq, Nq + M]; memories [M, dim] or [B, M, dim]
+per layer (`Transformer`: [depth, M, dim], [depth, B, M, dim] or a sequence).  Not with dropout > 0 in training, not under
+encoder.record_attention, not with a gradient sink.
 """
 from __future__ import annotations
 
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 from ._lib import PATCH_P1P2C
-from .encoder import WEIGHTS, AttnHalfFn, BlockMeta, EncoderStackFn, MlpHalfFn, PatchEmbedFn
+from .encoder import MASKS, WEIGHTS, AttnHalfFn, BlockMeta, EncoderStackFn, MemStackFn, MlpHalfFn, NrvError, PatchEmbedFn
 from .simple_vit import PatchUnfold, _pair
 
 
@@ -121,10 +127,41 @@ class Attention(nn.Module):
 
     def forward(self, x, attn_mask=None, memories=None):
         if attn_mask is not None or memories is not None:
-            raise NotImplementedError("attention masks / memory tokens are outside the encoder hot path")
+            self._meta.dropout = self._meta.attn_dropout = 0.0
+            _no_dropout(self.training, self.p)
+            mask, mems = _mem_inputs(x, self.heads, attn_mask, None if memories is None else [memories])
+            return MemStackFn.apply(x, self._meta, True, mask, len(mems), *mems, *self.layer_params())
         # stand-alone use: dropout on the attention weights (learnable_memory_vit.py:83; composed on the materialised matrix) and behind to_out (:61)
         self._meta.dropout = self._meta.attn_dropout = self.p if self.training else 0.0
         return AttnHalfFn.apply(x, self._meta, *self.layer_params())
+
+
+def _no_dropout(training: bool, p: float) -> None:
+    if training and p > 0.0:
+        raise NotImplementedError("dropout > 0 in training together with attention masks / memory tokens is not implemented")
+
+
+def _mem_inputs(x, heads: int, attn_mask, per_layer):
+    """(packed mask or None, per-layer memory tensors) for encoder.MemStackFn; the same M in every layer."""
+    if x.dim() != 3:
+        raise NrvError(f"expected (batch, tokens, dim), got {tuple(x.shape)}")
+    B, N, _ = x.shape
+    mems = []
+    if per_layer is not None:
+        for m in per_layer:
+            # 'n d -> b n d' (learnable_memory_vit.py:71) happens in the kernel: a stride of 0 rows per sample
+            if m.dim() not in (2, 3):
+                raise NrvError(f"memories of one layer must be [M, dim] or [B, M, dim], got {tuple(m.shape)}")
+            mems.append(m)
+        if len({m.shape[-2] for m in mems}) > 1:
+            raise NrvError("every layer needs the same number of memories")
+    M = mems[0].shape[-2] if mems else 0
+    mask = None
+    if attn_mask is not None:
+        if attn_mask.device != x.device:
+            raise NrvError("attn_mask must be on the device of the input")
+        mask = MASKS.get(attn_mask, B, heads, N, N + M)
+    return mask, mems
 
 
 class Transformer(nn.Module):
@@ -148,7 +185,17 @@ class Transformer(nn.Module):
 
     def forward(self, x, attn_mask=None, memories=None):
         if attn_mask is not None or memories is not None:
-            raise NotImplementedError("attention masks / memory tokens are outside the encoder hot path")
+            _no_dropout(self.training, self.p)
+            if self._meta.sink is not None:
+                raise NotImplementedError("memory keys / score masks are not wired to a gradient sink (data-parallel runtime)")
+            self._meta.dropout = self._meta.attn_dropout = 0.0
+            # memories[ind] per layer (learnable_memory_vit.py:101-102)
+            per_layer = None if memories is None else [memories[i] for i in range(len(self.layers))]
+            mask, mems = _mem_inputs(x, self._meta.heads, attn_mask, per_layer)
+            flat = []
+            for attn, ff in self.layers:
+                flat += attn.layer_params() + ff.layer_params()
+            return MemStackFn.apply(x, self._meta, False, mask, len(mems), *mems, *flat)
         # the one `dropout` of the reference's Transformer (learnable_memory_vit.py:90-96) sits at four places per layer: on the attention
         # weights (:83, composed on the materialised matrix), behind to_out (:61), behind the GELU (:37) and behind the second Linear (:39)
         self._meta.dropout = self._meta.attn_dropout = self.p if self.training else 0.0
@@ -196,3 +243,35 @@ class ViT(nn.Module):
     def forward(self, img):
         x = self.transformer(self.img_to_tokens(img))
         return self.mlp_head(x[:, 0])
+
+
+class Adapter(nn.Module):
+    """A frozen `ViT` fine-tuned through learnable memories (learnable_memory_vit.py:155-205): a memory CLS token in front of
+    the tokens, `num_memories_per_layer` extra key / value rows per layer, and a head of its own.  The mask keeps the image
+    tokens from seeing the memory CLS token and the memories, so the backbone's outputs for them are unchanged."""
+
+    def __init__(self, *, vit, num_memories_per_layer=10, num_classes=2):
+        super().__init__()
+        assert isinstance(vit, ViT)
+        dim = vit.cls_token.shape[-1]
+        layers = len(vit.transformer.layers)
+        num_patches = vit.pos_embedding.shape[-2]
+        self.vit = vit
+        for p in vit.parameters():                # freeze_all_layers_ (:17-24): only the memories and the head train
+            p.requires_grad = False
+        self.memory_cls_token = nn.Parameter(torch.randn(dim))
+        self.memories_per_layer = nn.Parameter(torch.randn(layers, num_memories_per_layer, dim))
+        self.mlp_head = nn.Sequential(nn.LayerNorm(dim), nn.Linear(dim, num_classes))
+        # row 0 (memory CLS) sees every key; rows 1 .. S see the S backbone tokens only (:186-193)
+        attn_mask = torch.ones((num_patches, num_patches), dtype=torch.bool)
+        attn_mask = F.pad(attn_mask, (1, num_memories_per_layer), value=False)
+        attn_mask = F.pad(attn_mask, (0, 0, 1, 0), value=True)
+        self.register_buffer('attn_mask', attn_mask)
+
+    def forward(self, img):
+        b = img.shape[0]
+        tokens = self.vit.img_to_tokens(img)
+        memory_cls_tokens = self.memory_cls_token.reshape(1, 1, -1).expand(b, 1, -1)
+        tokens = torch.cat((memory_cls_tokens, tokens), dim=1)
+        out = self.vit.transformer(tokens, memories=self.memories_per_layer, attn_mask=self.attn_mask)
+        return self.mlp_head(out[:, 0])

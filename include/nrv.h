@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NRV_ABI_VERSION 14
+#define NRV_ABI_VERSION 15
 
 /* dtype codes */
 #define NRV_F32 0
@@ -222,6 +222,43 @@ int nrv_attn_sinkhorn_fwd(const void* qkv_bf16, void* out_bf16, float* lse, floa
                           int B, int N, int H, int dh, float scale, void* stream);
 int nrv_attn_sinkhorn_bwd(const void* qkv_bf16, const void* dout_bf16, const float* lse, const float* scalings,
                           void* dqkv_bf16, int B, int N, int H, int dh, float scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Shifted-window attention of the Swin Transformer (ABI 15; swin.py:165-267 between the QKV and output Linears: torch.roll,
+ * window partition, q * dh^-0.5 @ k^T, + relative-position bias, + the -100 shift mask, softmax or Sinkhorn (swin.py:239-246),
+ * @ v, reverse partition, reverse roll).
+ *   The grid is the PADDED map pH x pW (multiples of Wh, Ww); its tokens are rows b*pH*pW + y*pW + x.
+ *   qkv bf16 [B*pH*pW, 3C] as the QKV GEMM writes it: feature which*C + h*dh + d (swin.py:187-189), dh = C / heads.
+ *   Slot (i, j) of window (wy, wx) is token ((wy*Wh + i + sh) mod pH, (wx*Ww + j + sw) mod pW); out bf16 [B*pH*pW, C] is written
+ *   to the same token rows, so the roll and the partition and their reverses are index arithmetic (no permuted copy).
+ *   table fp32 [(2Wh-1)(2Ww-1), heads] (relative_position_bias_table, indexed (dy + Wh-1)(2Ww-1) + dx + Ww-1 for the coordinate
+ *   difference query - key, swin.py:330-347).  sh, sw: the shift AFTER the reference's rule that zeroes it on an axis the window
+ *   covers (swin.py:157-161); the -100 mask between shift regions (swin.py:203-236) is applied when sh + sw > 0.
+ *   robust = 0: softmax; 1: softmax, 3 x (row /, column /), row / over the window matrix (padded slots take part).
+ *   stats fp32 [B*pH*pW, heads, S]: S = 1 (softmax: the row lse) or 8 (robust: lse, a1, b1, a2, b2, a3, b3, a4 -- the cumulative
+ *   scalings of nrv_attn_sinkhorn_fwd, a_t of the token as a query, b_t as a key).  Saved for the backward; nothing of size
+ *   [windows, heads, N, N] is stored.
+ *   Shapes: dh in {32, 64}, Wh * Ww <= 64, (2Wh-1)(2Ww-1) <= 225, 0 <= sh < Wh, 0 <= sw < Ww; else NRV_ERR_SHAPE.
+ *   qkv / out / dout / dqkv 16-byte aligned.
+ * Backward: dqkv bf16 [B*pH*pW, 3C] (every row written), dtable fp32 [(2Wh-1)(2Ww-1), heads] = the score gradient summed over
+ *   batch and windows and folded through the index: per-workgroup partials over fixed chunks of 8 windows in `workspace`
+ *   (nrv_window_attn_bwd_workspace bytes), then a fixed-order sum per entry.  Deterministic (no atomics). */
+int nrv_window_attn_fwd(const void* qkv_bf16, const float* table, void* out_bf16, float* stats,
+                        int B, int pH, int pW, int C, int heads, int Wh, int Ww, int sh, int sw, int robust, void* stream);
+size_t nrv_window_attn_bwd_workspace(int B, int pH, int pW, int C, int heads, int Wh, int Ww);
+int nrv_window_attn_bwd(const void* qkv_bf16, const float* table, const void* dout_bf16, const float* stats,
+                        void* dqkv_bf16, float* dtable, void* workspace, size_t workspace_bytes,
+                        int B, int pH, int pW, int C, int heads, int Wh, int Ww, int sh, int sw, int robust, void* stream);
+
+/* Stochastic depth, row mode (ABI 15; torchvision StochasticDepth(p, "row") at swin.py:519,532-533): one factor per sample,
+ * f = keep[r / rows_per_sample] / survival (keep fp32 [samples], 0 or 1, the caller's data; survival = 1 - p > 0).
+ *   nrv_sd_add_f32   : out = x + y * f          fp32 [rows, dim] (out may alias x or y)
+ *   nrv_sd_scale_bf16: out_bf16 = bf16(dy * f)  the branch gradient of the same add (feeds the branch's GEMMs)
+ *   dim % 4 == 0, rows % rows_per_sample == 0. */
+int nrv_sd_add_f32(const float* x, const float* y, const float* keep, float* out, float survival,
+                   int64_t rows, int64_t rows_per_sample, int dim, void* stream);
+int nrv_sd_scale_bf16(const float* dy, const float* keep, void* out_bf16, float survival,
+                      int64_t rows, int64_t rows_per_sample, int dim, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Stand-alone SinkhornAttention(scores)  (the reference's exported module, utils.py:1025-1037, applied to a MATERIALISED

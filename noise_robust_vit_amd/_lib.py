@@ -18,7 +18,7 @@ LIB_PATH = _DEFAULT_LIB       # no environment override: what runs is the in-tre
 NRV_F32, NRV_BF16, NRV_U8 = 0, 1, 2
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_DGELU, EPI_BIAS_GELU_Q8, EPI_DGELU_Q8 = 0, 1, 2, 3, 4, 5, 6
 PATCH_P1P2C, PATCH_CP1P2 = 0, 1
-ABI_VERSION = 14
+ABI_VERSION = 15
 ATTN_QKV_BLOCKED, ATTN_OUT_BLOCKED = 1, 2      # include/nrv.h: NRV_ATTN_*_BLOCKED
 
 
@@ -63,6 +63,13 @@ SIGNATURES = {
     "nrv_attn_sinkhorn_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "nrv_attn_sinkhorn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "nrv_window_attn_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, c_int, c_int, c_void_p]),
+    "nrv_window_attn_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "nrv_window_attn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "nrv_sd_add_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int64, c_int, c_void_p]),
+    "nrv_sd_scale_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int64, c_int, c_void_p]),
     "nrv_patch_unfold": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "nrv_cast_transpose": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "nrv_cast_transpose_batched": (c_int, [c_void_p, c_int, c_int64, c_void_p]),

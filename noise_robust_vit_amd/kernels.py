@@ -840,3 +840,97 @@ def run_cast_jobs(handle) -> None:
     lib = _lib.load()
     _run("cast_transpose", 0.0, 0.0, lambda: lib.nrv_cast_transpose_batched(table.data_ptr(), n, total, _stream()),
          "nrv_cast_transpose_batched")
+
+
+# ----------------------------------------------------------------------------------------------
+# Swin: shifted-window attention and row-mode stochastic depth (include/nrv.h, ABI 15)
+# ----------------------------------------------------------------------------------------------
+def _window_args(qkv: Tensor, B: int, pH: int, pW: int, C: int, heads: int, Wh: int, Ww: int, sh: int, sw: int) -> None:
+    _bf16(qkv, "qkv")
+    if not qkv.is_contiguous() or tuple(qkv.shape) != (B * pH * pW, 3 * C):
+        raise NrvError(f"window_attn: qkv must be contiguous [{B * pH * pW}, {3 * C}], got {tuple(qkv.shape)}")
+    if C % heads or C // heads not in (32, 64):
+        raise NrvError(f"window_attn: head dim C / heads = {C / heads} is not 32 or 64")
+    if Wh * Ww > 64 or pH % Wh or pW % Ww or not (0 <= sh < Wh) or not (0 <= sw < Ww):
+        raise NrvError(f"window_attn: window {Wh}x{Ww} (<= 64 slots) must tile the padded map {pH}x{pW}; shift ({sh}, {sw})")
+
+
+def window_attn_fwd(qkv: Tensor, table: Tensor, B: int, pH: int, pW: int, C: int, heads: int, window, shift, robust: bool):
+    """Shifted-window attention over the padded map (include/nrv.h nrv_window_attn_fwd).  Returns (out bf16 [B*pH*pW, C], stats)."""
+    Wh, Ww = window
+    sh, sw = shift
+    _window_args(qkv, B, pH, pW, C, heads, Wh, Ww, sh, sw)
+    _f32(table, "table")
+    if tuple(table.shape) != ((2 * Wh - 1) * (2 * Ww - 1), heads) or not table.is_contiguous():
+        raise NrvError(f"window_attn: table must be contiguous [{(2 * Wh - 1) * (2 * Ww - 1)}, {heads}], got {tuple(table.shape)}")
+    T = B * pH * pW
+    out = torch.empty(T, C, dtype=torch.bfloat16, device=qkv.device)
+    stats = torch.empty(T, heads, 8 if robust else 1, dtype=torch.float32, device=qkv.device)
+    lib = _lib.load()
+    N = Wh * Ww
+    _run("window_attn_fwd", 4.0 * T * N * C, T * C * 8 + stats.numel() * 4,
+         lambda: lib.nrv_window_attn_fwd(qkv.data_ptr(), table.data_ptr(), out.data_ptr(), stats.data_ptr(), B, pH, pW, C, heads,
+                                         Wh, Ww, sh, sw, int(bool(robust)), _stream()),
+         "nrv_window_attn_fwd")
+    return out, stats
+
+
+def window_attn_bwd(qkv: Tensor, table: Tensor, dout: Tensor, stats: Tensor, B: int, pH: int, pW: int, C: int, heads: int,
+                    window, shift, robust: bool):
+    """Returns (dqkv bf16 [B*pH*pW, 3C], dtable fp32 [(2Wh-1)(2Ww-1), heads]); deterministic."""
+    Wh, Ww = window
+    sh, sw = shift
+    _window_args(qkv, B, pH, pW, C, heads, Wh, Ww, sh, sw)
+    _bf16(dout, "dout"); _f32(stats, "stats"); _f32(table, "table")
+    T = B * pH * pW
+    if not dout.is_contiguous() or tuple(dout.shape) != (T, C):
+        raise NrvError(f"window_attn_bwd: dout must be contiguous [{T}, {C}], got {tuple(dout.shape)}")
+    if tuple(stats.shape) != (T, heads, 8 if robust else 1):
+        raise NrvError(f"window_attn_bwd: stats {tuple(stats.shape)} do not belong to this call")
+    lib = _lib.load()
+    wsb = lib.nrv_window_attn_bwd_workspace(B, pH, pW, C, heads, Wh, Ww)
+    ws = _workspace(wsb, qkv.device)
+    dqkv = torch.empty(T, 3 * C, dtype=torch.bfloat16, device=qkv.device)
+    dtable = torch.empty_like(table)
+    N = Wh * Ww
+    _run("window_attn_bwd", 10.0 * T * N * C, T * C * 16 + stats.numel() * 4,
+         lambda: lib.nrv_window_attn_bwd(qkv.data_ptr(), table.data_ptr(), dout.data_ptr(), stats.data_ptr(), dqkv.data_ptr(),
+                                         dtable.data_ptr(), ws.data_ptr(), wsb, B, pH, pW, C, heads, Wh, Ww, sh, sw,
+                                         int(bool(robust)), _stream()),
+         "nrv_window_attn_bwd")
+    return dqkv, dtable
+
+
+def _sd_args(x: Tensor, keep: Tensor, survival: float) -> Tuple[int, int]:
+    _f32(keep, "keep")
+    if not x.is_contiguous() or x.dim() != 2 or x.shape[1] % 4:
+        raise NrvError("stochastic depth: a contiguous [rows, dim] tensor with dim % 4 == 0")
+    if keep.dim() != 1 or not keep.is_contiguous() or x.shape[0] % keep.numel():
+        raise NrvError(f"stochastic depth: keep must be one value per sample, {keep.numel()} does not divide {x.shape[0]} rows")
+    if not survival > 0.0:
+        raise NrvError("stochastic depth: survival probability must be > 0")
+    return x.shape[0], x.shape[0] // keep.numel()
+
+
+def sd_add(x: Tensor, y: Tensor, keep: Tensor, survival: float, out: Optional[Tensor] = None) -> Tensor:
+    """out = x + y * keep[sample] / survival (include/nrv.h nrv_sd_add_f32)."""
+    _f32(x, "x"); _f32(y, "y")
+    rows, per = _sd_args(x, keep, survival)
+    if y.shape != x.shape or not y.is_contiguous():
+        raise NrvError("sd_add: y must match x")
+    o = torch.empty_like(x) if out is None else out
+    _run("sd_add", 0.0, x.numel() * 12,
+         lambda: _lib.load().nrv_sd_add_f32(x.data_ptr(), y.data_ptr(), keep.data_ptr(), o.data_ptr(), float(survival), rows, per,
+                                            x.shape[1], _stream()), "nrv_sd_add_f32")
+    return o
+
+
+def sd_scale_bf16(dy: Tensor, keep: Tensor, survival: float) -> Tensor:
+    """bf16(dy * keep[sample] / survival): the branch gradient of sd_add (include/nrv.h nrv_sd_scale_bf16)."""
+    _f32(dy, "dy")
+    rows, per = _sd_args(dy, keep, survival)
+    o = torch.empty(dy.shape, dtype=torch.bfloat16, device=dy.device)
+    _run("sd_scale", 0.0, dy.numel() * 6,
+         lambda: _lib.load().nrv_sd_scale_bf16(dy.data_ptr(), keep.data_ptr(), o.data_ptr(), float(survival), rows, per,
+                                               dy.shape[1], _stream()), "nrv_sd_scale_bf16")
+    return o

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Launches for a kernel trace (rocprofv3 --kernel-trace --stats -- python tools/attn_mem_profile.py): the memory / mask
-attention forward and backward against nrv_attn_fwd / nrv_attn_bwd at N = 197 (ViT-B/16: B 256, H 12, dh 64; the single-pass
-kernels) with M = 0 and with M = 10 plus the Adapter mask, and against the streaming kernels of nrv_attn_gen.hip at N = 300
-(which nrv_attn_fwd takes for N > 256) with M = 0, i.e. the same Nk."""
+attention forward and backward (nrv_attn_mem_*) against nrv_attn_fwd / nrv_attn_bwd at N = 197 (ViT-B/16: B 256, H 12, dh 64;
+the single-pass kernels) with M = 0 and with M = 10 plus the Adapter mask, and at N = 300 (which nrv_attn_fwd takes to the
+streaming kernels of nrv_attn_gen.hip) with M = 0.  nrv_attn_mem_* run the MEM = false instantiation of those streaming
+kernels when M = 0 and there is no mask, the MEM = true one otherwise."""
 import os
 import sys
 

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NRV_ABI_VERSION 15
+#define NRV_ABI_VERSION 16
 
 /* dtype codes */
 #define NRV_F32 0
@@ -259,6 +259,79 @@ int nrv_sd_add_f32(const float* x, const float* y, const float* keep, float* out
                    int64_t rows, int64_t rows_per_sample, int dim, void* stream);
 int nrv_sd_scale_bf16(const float* dy, const float* keep, void* out_bf16, float survival,
                       int64_t rows, int64_t rows_per_sample, int dim, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * LeViT (ABI 16; levit.py).  Every Conv2d / Linear of LeViT is followed by a BatchNorm in training mode that normalises over
+ * all token rows; the stem keeps its activations as NHWC rows, so Conv2d_BN (levit.py:57-100) and Linear_BN (:103-134) are
+ * both "GEMM on rows (nrv_gemm_nt_bf16, fp32 out) -> BN over rows".
+ *
+ * Batch norm over rows, y fp32 [T, C] contiguous (replaces BatchNorm2d / BatchNorm1d at levit.py:70-71,106-107,133 and their
+ * backward).  C % 4 == 0, T <= 2^24; y, residual, out_f32 16-byte aligned, out_bf16 8-byte aligned.
+ *   nrv_bn_stats : per column mean and biased variance from per-chunk (count, mean, M2) partials merged in a fixed order (Chan);
+ *                  mean, invstd = 1 / sqrt(var + eps) [C]; stat [3, C] = the combined (count, mean, M2) (what a cross-rank
+ *                  all-reduce would merge); running_mean / running_var (both or neither) updated with `momentum` and the
+ *                  unbiased variance.  workspace: nrv_bn_workspace(T, C) bytes.
+ *   nrv_bn_apply : z = gamma (y - mean) * inv + beta, inv = scale (scale_is_var = 0: invstd of nrv_bn_stats) or
+ *                  1 / sqrt(scale + eps) (scale_is_var = 1: the running variance, eval mode); act 1: z = hardswish(z);
+ *                  keep (optional, fp32 [T / rows_per_sample]): z *= keep[r / rows_per_sample] / survival (row-mode drop-path,
+ *                  levit.py:187-193); residual (optional, fp32 [T, C]): z += residual.  Stores out_f32 and / or out_bf16.
+ *   nrv_bn_bwd   : dz = upstream (dz_dtype fp32|bf16 [T, C]) * hardswish'(z) (act 1) * keep factor; dgamma = sum dz x^,
+ *                  dbeta = sum dz (fixed-order partials); dy_bf16 = gamma inv (dz - mean(dz) - x^ mean(dz x^)) (training = 1) or
+ *                  gamma inv dz (training = 0).  Same workspace.  Deterministic (no atomics). */
+size_t nrv_bn_workspace(int64_t T, int C);
+int nrv_bn_stats(const float* y, int64_t T, int C, float eps, float momentum,
+                 float* mean, float* invstd, float* stat, float* running_mean, float* running_var,
+                 void* workspace, size_t workspace_bytes, void* stream);
+int nrv_bn_apply(const float* y, const float* mean, const float* scale, int scale_is_var, float eps,
+                 const float* gamma, const float* beta, int act,
+                 const float* residual, const float* keep, float survival, int64_t rows_per_sample,
+                 float* out_f32, void* out_bf16, int64_t T, int C, void* stream);
+int nrv_bn_bwd(const void* dz, int dz_dtype, int act, const float* keep, float survival, int64_t rows_per_sample,
+               const float* y, const float* mean, const float* scale, int scale_is_var, float eps,
+               const float* gamma, const float* beta, int training,
+               float* dgamma, float* dbeta, void* dy_bf16,
+               void* workspace, size_t workspace_bytes, int64_t T, int C, void* stream);
+
+/* Convolution as unfold + GEMM (the b16 stem, levit.py:166-175: Conv2d(ks 3, stride 2, pad 1, no bias)).
+ *   nrv_conv_unfold: src = NCHW image (src_layout NRV_CONV_NCHW, fp32|bf16) or NHWC rows bf16 [B*H*W, C] (NRV_CONV_NHWC) ->
+ *                    cols bf16 [B*Ho*Wo, KP], feature (ky, kx, c), KP = ks*ks*C rounded up to 8, zero padding and zero
+ *                    columns >= ks*ks*C.  The GEMM weight image is the Conv2d weight permuted to [Cout, ks, ks, C].
+ *   nrv_conv_fold  : the input gradient, dx fp32 NHWC rows [B*H*W, C] from dcols bf16 [B*Ho*Wo, KP], in gather form: each
+ *                    input element sums its (ky, kx) contributions in ky-then-kx order (no scatter, no atomics).
+ *   Ho = (H + 2 pad - ks) / stride + 1; ks <= 7, pad < ks.  cols 16-byte aligned (and src for NHWC). */
+#define NRV_CONV_NCHW 0
+#define NRV_CONV_NHWC 1
+int nrv_conv_unfold(const void* src, int src_dtype, int src_layout, void* cols_bf16,
+                    int B, int C, int H, int W, int ks, int stride, int pad, void* stream);
+int nrv_conv_fold(const void* dcols_bf16, float* dx, int B, int C, int H, int W, int ks, int stride, int pad, void* stream);
+
+/* LeViT attention with a learned offset bias (levit.py:240-258 Attention, :380-403 AttentionSubsample, between qkv / q, kv and
+ * proj): S = kd^-0.5 q k^T + table[h, idx[i, j]]; robust = 0: softmax; 1: softmax, 3 x (row /, column /), row /; O = P V;
+ * act = hardswish(O) (the proj's activation, levit.py:229-232).
+ *   q / k / v: bf16 rows of sample b, token i, head h at base + (b * Nq|Nk + i) * ld + h * hstride (elements; ld, hstride % 8
+ *   == 0, bases 16-byte aligned): Attention's qkv [B*N, H*(2kd + d)] is q = qkv, k = qkv + kd, v = qkv + 2kd, hstride 2kd + d;
+ *   AttentionSubsample's q [B*Nq, H*kd] and kv [B*Nk, H*(kd + d)].  table fp32 [H, n_offsets] (attention_biases);
+ *   idx int32 [Nq, Nk] (attention_bias_idxs).  out, act bf16 [B*Nq, H*d] (column h*d + j, levit.py:256).
+ *   stats fp32 [B*H, nrv_bias_attn_stats_size(Nq, Nk, robust)]: lse [Nq]; Sinkhorn adds a1..a4 [4][Nq] and b1..b3 [3][Nk].
+ *   Shapes: Nq <= Nk <= 256, kd in {16, 32}, d in {32, 64, 128}, n_offsets <= 256, Nq * (Nk + 1) <= 39 424 (the fp32 score
+ *   matrix of one (sample, head) in LDS); else NRV_ERR_SHAPE.
+ * Backward: dact bf16 [B*Nq, H*d] = gradient of act (Hardswish' of the saved out applied on load); dq / dk / dv written in the
+ *   layouts of q / k / v (same ld and hstride; every row of every head written).  dtable fp32 [H, n_offsets] = dS summed over the
+ *   batch and folded through idx: inv_ptr int32 [n_offsets + 1] / inv_pos int32 [Nq*Nk] list the flat positions i*Nk + j of each
+ *   entry; per-(head, entry, sample) partials in workspace (nrv_bias_attn_bwd_workspace bytes), then a fixed-order sum over the
+ *   samples.  Deterministic (no atomics). */
+size_t nrv_bias_attn_stats_size(int Nq, int Nk, int robust);
+int nrv_bias_attn_fwd(const void* q, int64_t ldq, int hq, const void* k, int64_t ldk, int hk,
+                      const void* v, int64_t ldv, int hv, const float* table, const int32_t* idx,
+                      void* out_bf16, void* act_bf16, float* stats,
+                      int B, int heads, int Nq, int Nk, int kd, int dv, int n_offsets, int robust, void* stream);
+size_t nrv_bias_attn_bwd_workspace(int B, int heads, int n_offsets);
+int nrv_bias_attn_bwd(const void* q, int64_t ldq, int hq, const void* k, int64_t ldk, int hk,
+                      const void* v, int64_t ldv, int hv, const float* table, const int32_t* idx,
+                      const int32_t* inv_ptr, const int32_t* inv_pos,
+                      const void* out_bf16, const void* dact_bf16, const float* stats,
+                      void* dq, void* dk, void* dv_out, float* dtable, void* workspace, size_t workspace_bytes,
+                      int B, int heads, int Nq, int Nk, int kd, int dv, int n_offsets, int robust, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Stand-alone SinkhornAttention(scores)  (the reference's exported module, utils.py:1025-1037, applied to a MATERIALISED

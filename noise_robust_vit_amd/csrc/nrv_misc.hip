@@ -246,6 +246,84 @@ __global__ __launch_bounds__(64) void probe_kernel(int which, const bf16_t* __re
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// convolution as unfold + GEMM (LeViT's b16 stem, levit.py:166-175: Conv2d(3x3, stride 2, pad 1) without bias)
+//   unfold: src (NCHW image, fp32|bf16, or NHWC rows bf16 [B*H*W, C]) -> cols bf16 [B*Ho*Wo, KP], feature (ky, kx, c),
+//           KP = ks*ks*C rounded up to 8; padding and columns >= ks*ks*C read as zero
+//   fold  : the input gradient in gather form: dx[b, y, x, c] = sum over the (ky, kx) with (y + pad - ky) / stride = oy in
+//           range (and exact) of dcols[(b, oy, ox), (ky, kx, c)], ky then kx ascending (a fixed order; no scatter)
+// one thread = 8 consecutive output features of unfold, one input element of fold
+// ---------------------------------------------------------------------------------------------
+struct ConvGeom {
+    int B, C, H, W, Ho, Wo, ks, stride, pad, KP;
+};
+
+template <int SRC>      // 0: NCHW fp32, 1: NCHW bf16, 2: NHWC bf16 rows
+__device__ __forceinline__ float conv_src(const void* src, const ConvGeom& g, int b, int c, int iy, int ix) {
+    if (SRC == 0) return reinterpret_cast<const float*>(src)[(((long long)b * g.C + c) * g.H + iy) * g.W + ix];
+    if (SRC == 1) return bf16_to_f32(reinterpret_cast<const bf16_t*>(src)[(((long long)b * g.C + c) * g.H + iy) * g.W + ix]);
+    return bf16_to_f32(reinterpret_cast<const bf16_t*>(src)[(((long long)b * g.H + iy) * g.W + ix) * g.C + c]);
+}
+
+template <int SRC>
+__global__ __launch_bounds__(256) void conv_unfold_kernel(const void* __restrict__ src, bf16_t* __restrict__ out, ConvGeom g) {
+    const int F = g.ks * g.ks * g.C, F8 = g.KP >> 3;
+    const long long total = (long long)g.B * g.Ho * g.Wo * F8;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long t = i / F8;
+        const int f0 = (int)(i - t * F8) * 8;
+        const int b = (int)(t / ((long long)g.Ho * g.Wo));
+        const int rem = (int)(t - (long long)b * g.Ho * g.Wo);
+        const int oy = rem / g.Wo, ox = rem - (rem / g.Wo) * g.Wo;
+        if (SRC == 2 && (g.C & 7) == 0) {
+            // 8 channels of one tap: one 16-byte load of the NHWC row
+            const int k = f0 / g.C, c = f0 - k * g.C;
+            const int iy = oy * g.stride - g.pad + k / g.ks, ix = ox * g.stride - g.pad + k % g.ks;
+            u32x4_t v = {0u, 0u, 0u, 0u};
+            if (f0 < F && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W)
+                v = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const bf16_t*>(src) + (((long long)b * g.H + iy) * g.W + ix) * g.C + c);
+            *reinterpret_cast<u32x4_t*>(out + t * g.KP + f0) = v;
+            continue;
+        }
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int f = f0 + j;
+            const int k = f / g.C, c = f - k * g.C;
+            const int iy = oy * g.stride - g.pad + k / g.ks, ix = ox * g.stride - g.pad + k % g.ks;
+            v[j] = (f < F && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W) ? conv_src<SRC>(src, g, b, c, iy, ix) : 0.f;
+        }
+        u32x4_t pk = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+        *reinterpret_cast<u32x4_t*>(out + t * g.KP + f0) = pk;
+    }
+}
+
+__global__ __launch_bounds__(256) void conv_fold_kernel(const bf16_t* __restrict__ dcols, float* __restrict__ dx, ConvGeom g) {
+    const long long total = (long long)g.B * g.H * g.W * g.C;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long pix = i / g.C;
+        const int c = (int)(i - pix * g.C);
+        const int b = (int)(pix / ((long long)g.H * g.W));
+        const int rem = (int)(pix - (long long)b * g.H * g.W);
+        const int y = rem / g.W, x = rem - (rem / g.W) * g.W;
+        float acc = 0.f;
+        for (int ky = 0; ky < g.ks; ++ky) {
+            const int ny = y + g.pad - ky;
+            if (ny < 0 || ny % g.stride) continue;
+            const int oy = ny / g.stride;
+            if (oy >= g.Ho) continue;
+            for (int kx = 0; kx < g.ks; ++kx) {
+                const int nx = x + g.pad - kx;
+                if (nx < 0 || nx % g.stride) continue;
+                const int ox = nx / g.stride;
+                if (ox >= g.Wo) continue;
+                acc += bf16_to_f32(dcols[(((long long)b * g.Ho + oy) * g.Wo + ox) * g.KP + (ky * g.ks + kx) * g.C + c]);
+            }
+        }
+        dx[i] = acc;
+    }
+}
+
 int grid_for(long long work_items, int block) {
     long long g = (work_items + block - 1) / block;
     if (g > 4096) g = 4096;
@@ -288,6 +366,46 @@ extern "C" int nrv_patch_unfold(const void* img, int img_dtype, void* patches_bf
         if (layout == NRV_PATCH_P1P2C) hipLaunchKernelGGL((patch_unfold_kernel<false, NRV_PATCH_P1P2C>), dim3(grid), dim3(256), 0, s, img, out, B, C, H, W, p);
         else hipLaunchKernelGGL((patch_unfold_kernel<false, NRV_PATCH_CP1P2>), dim3(grid), dim3(256), 0, s, img, out, B, C, H, W, p);
     }
+    NRV_CHECK_LAUNCH();
+    return 0;
+}
+
+static int conv_geom(ConvGeom& g, int B, int C, int H, int W, int ks, int stride, int pad) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ks <= 0 || ks > 7 || stride <= 0 || pad < 0 || pad >= ks) return NRV_ERR_SHAPE;
+    if (H + 2 * pad < ks || W + 2 * pad < ks) return NRV_ERR_SHAPE;
+    g.B = B; g.C = C; g.H = H; g.W = W; g.ks = ks; g.stride = stride; g.pad = pad;
+    g.Ho = (H + 2 * pad - ks) / stride + 1;
+    g.Wo = (W + 2 * pad - ks) / stride + 1;
+    g.KP = (ks * ks * C + 7) & ~7;
+    if ((long long)B * g.Ho * g.Wo * g.KP > (1ll << 40) || (long long)B * H * W * C > (1ll << 40)) return NRV_ERR_SHAPE;
+    return 0;
+}
+
+extern "C" int nrv_conv_unfold(const void* src, int src_dtype, int src_layout, void* cols_bf16,
+                               int B, int C, int H, int W, int ks, int stride, int pad, void* stream) {
+    ConvGeom g{};
+    if (conv_geom(g, B, C, H, W, ks, stride, pad)) return NRV_ERR_SHAPE;
+    if (!src || !cols_bf16) return NRV_ERR_NULL;
+    if (src_layout != NRV_CONV_NCHW && src_layout != NRV_CONV_NHWC) return NRV_ERR_SHAPE;
+    if (src_dtype != NRV_F32 && src_dtype != NRV_BF16) return NRV_ERR_DTYPE;
+    if (src_layout == NRV_CONV_NHWC && src_dtype != NRV_BF16) return NRV_ERR_DTYPE;
+    if (!nrv_aligned16(cols_bf16) || (src_layout == NRV_CONV_NHWC && !nrv_aligned16(src))) return NRV_ERR_ALIGN;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int grid = grid_for((long long)B * g.Ho * g.Wo * (g.KP >> 3), 256);
+    bf16_t* out = static_cast<bf16_t*>(cols_bf16);
+    if (src_layout == NRV_CONV_NHWC) hipLaunchKernelGGL((conv_unfold_kernel<2>), dim3(grid), dim3(256), 0, s, src, out, g);
+    else if (src_dtype == NRV_F32) hipLaunchKernelGGL((conv_unfold_kernel<0>), dim3(grid), dim3(256), 0, s, src, out, g);
+    else hipLaunchKernelGGL((conv_unfold_kernel<1>), dim3(grid), dim3(256), 0, s, src, out, g);
+    NRV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nrv_conv_fold(const void* dcols_bf16, float* dx, int B, int C, int H, int W, int ks, int stride, int pad, void* stream) {
+    ConvGeom g{};
+    if (conv_geom(g, B, C, H, W, ks, stride, pad)) return NRV_ERR_SHAPE;
+    if (!dcols_bf16 || !dx) return NRV_ERR_NULL;
+    hipLaunchKernelGGL(conv_fold_kernel, dim3(grid_for((long long)B * H * W * C, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const bf16_t*>(dcols_bf16), dx, g);
     NRV_CHECK_LAUNCH();
     return 0;
 }

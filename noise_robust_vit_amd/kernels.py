@@ -934,3 +934,211 @@ def sd_scale_bf16(dy: Tensor, keep: Tensor, survival: float) -> Tensor:
          lambda: _lib.load().nrv_sd_scale_bf16(dy.data_ptr(), keep.data_ptr(), o.data_ptr(), float(survival), rows, per,
                                                dy.shape[1], _stream()), "nrv_sd_scale_bf16")
     return o
+
+
+# ----------------------------------------------------------------------------------------------
+# LeViT (ABI 16): batch norm over rows, convolution as unfold + GEMM, attention with a learned offset bias
+# ----------------------------------------------------------------------------------------------
+def _bn_rows(y: Tensor, name: str) -> Tuple[int, int]:
+    _f32(y, name)
+    if y.dim() != 2 or not y.is_contiguous() or y.shape[1] % 4:
+        raise NrvError(f"batch norm: {name} must be contiguous fp32 [T, C] with C % 4 == 0, got {tuple(y.shape)}")
+    return y.shape[0], y.shape[1]
+
+
+def _bn_keep(keep: Optional[Tensor], T: int) -> int:
+    if keep is None:
+        return 1
+    _f32(keep, "keep")
+    if keep.dim() != 1 or not keep.is_contiguous() or T % keep.numel():
+        raise NrvError(f"batch norm: keep must be one value per sample, {keep.numel()} does not divide {T} rows")
+    return T // keep.numel()
+
+
+def bn_stats(y: Tensor, eps: float, momentum: float, running_mean: Optional[Tensor] = None,
+             running_var: Optional[Tensor] = None):
+    """Training-mode statistics of y [T, C] (include/nrv.h nrv_bn_stats); updates the running buffers in place when given.
+    Returns (mean, invstd, stat [3, C] = the combined (count, mean, M2))."""
+    T, C = _bn_rows(y, "y")
+    for t, n in ((running_mean, "running_mean"), (running_var, "running_var")):
+        if t is not None:
+            _f32(t, n)
+            if t.numel() != C or not t.is_contiguous():
+                raise NrvError(f"bn_stats: {n} must hold {C} contiguous floats")
+    mean = torch.empty(C, dtype=torch.float32, device=y.device)
+    invstd = torch.empty_like(mean)
+    stat = torch.empty(3, C, dtype=torch.float32, device=y.device)
+    lib = _lib.load()
+    wsb = lib.nrv_bn_workspace(T, C)
+    ws = _workspace(wsb, y.device)
+    _run("bn_stats", 4.0 * T * C, 4 * T * C,
+         lambda: lib.nrv_bn_stats(y.data_ptr(), T, C, float(eps), float(momentum), mean.data_ptr(), invstd.data_ptr(),
+                                  stat.data_ptr(), _ptr(running_mean), _ptr(running_var), ws.data_ptr(), wsb, _stream()),
+         "nrv_bn_stats")
+    return mean, invstd, stat
+
+
+def bn_apply(y: Tensor, mean: Tensor, scale: Tensor, gamma: Tensor, beta: Tensor, *, eps: float = 0.0, scale_is_var: bool = False,
+             act: bool = False, residual: Optional[Tensor] = None, keep: Optional[Tensor] = None, survival: float = 1.0,
+             want_f32: bool = False, want_bf16: bool = True):
+    """z = gamma (y - mean) inv + beta [-> hardswish] [* keep / survival] [+ residual] (include/nrv.h nrv_bn_apply).
+    Returns (z fp32 or None, z bf16 or None)."""
+    T, C = _bn_rows(y, "y")
+    for t, n in ((mean, "mean"), (scale, "scale"), (gamma, "gamma"), (beta, "beta")):
+        _f32(t, n)
+        if t.numel() != C or not t.is_contiguous():
+            raise NrvError(f"bn_apply: {n} must hold {C} contiguous floats")
+    if residual is not None:
+        _f32(residual, "residual")
+        if residual.shape != y.shape or not residual.is_contiguous():
+            raise NrvError("bn_apply: residual must match y")
+    per = _bn_keep(keep, T)
+    o32 = torch.empty(T, C, dtype=torch.float32, device=y.device) if want_f32 else None
+    o16 = torch.empty(T, C, dtype=torch.bfloat16, device=y.device) if want_bf16 else None
+    _run("bn_apply", 4.0 * T * C, T * C * (4 + (4 if want_f32 else 0) + (2 if want_bf16 else 0) + (4 if residual is not None else 0)),
+         lambda: _lib.load().nrv_bn_apply(y.data_ptr(), mean.data_ptr(), scale.data_ptr(), int(scale_is_var), float(eps),
+                                          gamma.data_ptr(), beta.data_ptr(), int(bool(act)), _ptr(residual), _ptr(keep),
+                                          float(survival), per, _ptr(o32), _ptr(o16), T, C, _stream()),
+         "nrv_bn_apply")
+    return o32, o16
+
+
+def bn_bwd(dz: Tensor, y: Tensor, mean: Tensor, scale: Tensor, gamma: Tensor, beta: Tensor, *, eps: float = 0.0,
+           scale_is_var: bool = False, act: bool = False, keep: Optional[Tensor] = None, survival: float = 1.0,
+           training: bool = True):
+    """Backward of bn_apply without the residual (include/nrv.h nrv_bn_bwd): returns (dy bf16 [T, C], dgamma, dbeta)."""
+    T, C = _bn_rows(y, "y")
+    _dev(dz, "dz")
+    if dz.shape != y.shape or not dz.is_contiguous():
+        raise NrvError("bn_bwd: dz must match y")
+    per = _bn_keep(keep, T)
+    dy = torch.empty(T, C, dtype=torch.bfloat16, device=y.device)
+    dg = torch.empty(C, dtype=torch.float32, device=y.device)
+    db = torch.empty_like(dg)
+    lib = _lib.load()
+    wsb = lib.nrv_bn_workspace(T, C)
+    ws = _workspace(wsb, y.device)
+    _run("bn_bwd", 10.0 * T * C, T * C * (8 + 2 * dz.element_size() + 2),
+         lambda: lib.nrv_bn_bwd(dz.data_ptr(), _dt(dz, "dz"), int(bool(act)), _ptr(keep), float(survival), per,
+                                y.data_ptr(), mean.data_ptr(), scale.data_ptr(), int(scale_is_var), float(eps),
+                                gamma.data_ptr(), beta.data_ptr(), int(bool(training)), dg.data_ptr(), db.data_ptr(),
+                                dy.data_ptr(), ws.data_ptr(), wsb, T, C, _stream()),
+         "nrv_bn_bwd")
+    return dy, dg, db
+
+
+def conv_out_size(n: int, ks: int, stride: int, pad: int) -> int:
+    return (n + 2 * pad - ks) // stride + 1
+
+
+def conv_unfold(src: Tensor, B: int, C: int, H: int, W: int, ks: int, stride: int, pad: int, nhwc: bool) -> Tensor:
+    """cols bf16 [B*Ho*Wo, KP], feature (ky, kx, c) (include/nrv.h nrv_conv_unfold); src NCHW image or NHWC rows bf16."""
+    _dev(src, "src")
+    if not src.is_contiguous() or src.numel() != B * C * H * W:
+        raise NrvError(f"conv_unfold: src must be contiguous with {B}x{C}x{H}x{W} elements, got {tuple(src.shape)}")
+    Ho, Wo = conv_out_size(H, ks, stride, pad), conv_out_size(W, ks, stride, pad)
+    KP = (ks * ks * C + 7) // 8 * 8
+    cols = torch.empty(B * Ho * Wo, KP, dtype=torch.bfloat16, device=src.device)
+    layout = _lib.CONV_NHWC if nhwc else _lib.CONV_NCHW
+    _run("conv_unfold", 0.0, cols.numel() * 2 + src.numel() * src.element_size(),
+         lambda: _lib.load().nrv_conv_unfold(src.data_ptr(), _dt(src, "src"), layout, cols.data_ptr(), B, C, H, W, ks, stride, pad,
+                                             _stream()),
+         "nrv_conv_unfold")
+    return cols
+
+
+def conv_fold(dcols: Tensor, B: int, C: int, H: int, W: int, ks: int, stride: int, pad: int) -> Tensor:
+    """dx fp32 NHWC rows [B*H*W, C] (include/nrv.h nrv_conv_fold)."""
+    _bf16(dcols, "dcols")
+    Ho, Wo = conv_out_size(H, ks, stride, pad), conv_out_size(W, ks, stride, pad)
+    KP = (ks * ks * C + 7) // 8 * 8
+    if not dcols.is_contiguous() or tuple(dcols.shape) != (B * Ho * Wo, KP):
+        raise NrvError(f"conv_fold: dcols must be contiguous [{B * Ho * Wo}, {KP}], got {tuple(dcols.shape)}")
+    dx = torch.empty(B * H * W, C, dtype=torch.float32, device=dcols.device)
+    _run("conv_fold", 0.0, dcols.numel() * 2 + dx.numel() * 4,
+         lambda: _lib.load().nrv_conv_fold(dcols.data_ptr(), dx.data_ptr(), B, C, H, W, ks, stride, pad, _stream()),
+         "nrv_conv_fold")
+    return dx
+
+
+@dataclass
+class BiasIndex:
+    """Device copies of one geometry's bias index: idx int32 [Nq, Nk] and its inverse (CSR over the table entries)."""
+    idx: Tensor
+    inv_ptr: Tensor
+    inv_pos: Tensor
+    n_offsets: int
+
+
+def bias_index(idx: Tensor, n_offsets: int, device) -> BiasIndex:
+    """Build the int32 index and its inverse from an int64 [Nq, Nk] attention_bias_idxs (host arithmetic, once per geometry).
+    Entries outside [0, n_offsets) are refused here, before any kernel reads them."""
+    import numpy as np
+    a = idx.detach().to("cpu", torch.int64).numpy()       # numpy, not torch: nothing here is dispatched as a (capturable) op
+    if a.ndim != 2:
+        raise NrvError(f"bias index must be [Nq, Nk], got {a.shape}")
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= n_offsets):
+        raise NrvError(f"bias index holds entries outside [0, {n_offsets})")
+    flat = a.reshape(-1)
+    order = np.argsort(flat, kind="stable").astype(np.int32)
+    ptr = np.zeros(n_offsets + 1, dtype=np.int32)
+    ptr[1:] = np.cumsum(np.bincount(flat, minlength=n_offsets))
+    return BiasIndex(torch.from_numpy(a.astype(np.int32)).to(device), torch.from_numpy(ptr).to(device),
+                     torch.from_numpy(order).to(device), int(n_offsets))
+
+
+def _qkv_view(t: Tensor, rows: int, name: str) -> int:
+    _bf16(t, name)
+    if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != rows:
+        raise NrvError(f"bias_attn: {name} must be a row-major [{rows}, *] view, got {tuple(t.shape)}")
+    return t.stride(0)
+
+
+def bias_attn_fwd(q: Tensor, k: Tensor, v: Tensor, hq: int, hk: int, hv: int, table: Tensor, index: BiasIndex,
+                  B: int, H: int, Nq: int, Nk: int, kd: int, d: int, robust: bool):
+    """q / k / v: [B*Nq|Nk, *] bf16 views whose first column is head 0's q / k / v, heads hq / hk / hv columns apart
+    (include/nrv.h nrv_bias_attn_fwd).  Returns (o bf16 [B*Nq, H*d], hardswish(o) bf16, stats fp32 [B*H, S])."""
+    ldq = _qkv_view(q, B * Nq, "q"); ldk = _qkv_view(k, B * Nk, "k"); ldv = _qkv_view(v, B * Nk, "v")
+    _f32(table, "table")
+    if tuple(table.shape) != (H, index.n_offsets) or not table.is_contiguous():
+        raise NrvError(f"bias_attn: table must be contiguous [{H}, {index.n_offsets}], got {tuple(table.shape)}")
+    if tuple(index.idx.shape) != (Nq, Nk):
+        raise NrvError(f"bias_attn: index {tuple(index.idx.shape)} does not belong to ({Nq}, {Nk})")
+    lib = _lib.load()
+    S = lib.nrv_bias_attn_stats_size(Nq, Nk, int(bool(robust)))
+    o = torch.empty(B * Nq, H * d, dtype=torch.bfloat16, device=q.device)
+    ao = torch.empty_like(o)
+    stats = torch.empty(B * H, S, dtype=torch.float32, device=q.device)
+    _run("bias_attn_fwd", 2.0 * B * H * Nq * Nk * (kd + d), 2 * (B * Nq * H * (kd + 2 * d) + B * Nk * H * (kd + d)),
+         lambda: lib.nrv_bias_attn_fwd(q.data_ptr(), ldq, hq, k.data_ptr(), ldk, hk, v.data_ptr(), ldv, hv, table.data_ptr(),
+                                       index.idx.data_ptr(), o.data_ptr(), ao.data_ptr(), stats.data_ptr(),
+                                       B, H, Nq, Nk, kd, d, index.n_offsets, int(bool(robust)), _stream()),
+         "nrv_bias_attn_fwd")
+    return o, ao, stats
+
+
+def bias_attn_bwd(q: Tensor, k: Tensor, v: Tensor, hq: int, hk: int, hv: int, table: Tensor, index: BiasIndex,
+                  o: Tensor, dact: Tensor, stats: Tensor, dq: Tensor, dk: Tensor, dv: Tensor,
+                  B: int, H: int, Nq: int, Nk: int, kd: int, d: int, robust: bool) -> Tensor:
+    """Writes dq / dk / dv (views laid out like q / k / v) and returns dtable fp32 [H, n_offsets]; deterministic."""
+    ldq = _qkv_view(q, B * Nq, "q"); ldk = _qkv_view(k, B * Nk, "k"); ldv = _qkv_view(v, B * Nk, "v")
+    if _qkv_view(dq, B * Nq, "dq") != ldq or _qkv_view(dk, B * Nk, "dk") != ldk or _qkv_view(dv, B * Nk, "dv") != ldv:
+        raise NrvError("bias_attn_bwd: the gradients must be laid out like q / k / v")
+    for t, n in ((o, "o"), (dact, "dact")):
+        _bf16(t, n)
+        if tuple(t.shape) != (B * Nq, H * d) or not t.is_contiguous():
+            raise NrvError(f"bias_attn_bwd: {n} must be contiguous [{B * Nq}, {H * d}]")
+    lib = _lib.load()
+    if tuple(stats.shape) != (B * H, lib.nrv_bias_attn_stats_size(Nq, Nk, int(bool(robust)))):
+        raise NrvError("bias_attn_bwd: stats do not belong to this call")
+    wsb = lib.nrv_bias_attn_bwd_workspace(B, H, index.n_offsets)
+    ws = _workspace(wsb, q.device)
+    dtable = torch.empty_like(table)
+    _run("bias_attn_bwd", 4.0 * B * H * Nq * Nk * (kd + d), 4 * (B * Nq * H * (kd + 2 * d) + B * Nk * H * (kd + d)),
+         lambda: lib.nrv_bias_attn_bwd(q.data_ptr(), ldq, hq, k.data_ptr(), ldk, hk, v.data_ptr(), ldv, hv, table.data_ptr(),
+                                       index.idx.data_ptr(), index.inv_ptr.data_ptr(), index.inv_pos.data_ptr(),
+                                       o.data_ptr(), dact.data_ptr(), stats.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+                                       dtable.data_ptr(), ws.data_ptr(), wsb, B, H, Nq, Nk, kd, d, index.n_offsets,
+                                       int(bool(robust)), _stream()),
+         "nrv_bias_attn_bwd")
+    return dtable

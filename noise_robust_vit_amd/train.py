@@ -193,6 +193,7 @@ class Trainer:
             raise RuntimeError("Trainer.capture: collectives are not captured; use the eager step with a process group")
         opt = self.opt
         saved = (opt.param.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone(), opt.step_count, self.step_idx)
+        buffers = [(b, b.clone()) for b in self.model.buffers()]      # batch-norm running statistics move in the warm-up steps
         rng_state = torch.cuda.get_rng_state(x.device)
         self._gx, self._gy = x.clone(), y.clone()
 
@@ -231,6 +232,9 @@ class Trainer:
             cur.wait_stream(side)
             with torch.no_grad():
                 opt.param.copy_(saved[0]); opt.exp_avg.copy_(saved[1]); opt.exp_avg_sq.copy_(saved[2])
+                for b, v in buffers:
+                    if not torch.equal(b, v):           # untouched buffers (index tables) keep their version counters
+                        b.copy_(v)
             opt.step_count, self.step_idx = saved[3], saved[4]
             torch.cuda.set_rng_state(rng_state, x.device)
             from .encoder import WEIGHTS

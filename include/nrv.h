@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NRV_ABI_VERSION 16
+#define NRV_ABI_VERSION 17
 
 /* dtype codes */
 #define NRV_F32 0
@@ -332,6 +332,71 @@ int nrv_bias_attn_bwd(const void* q, int64_t ldq, int hq, const void* k, int64_t
                       const void* out_bf16, const void* dact_bf16, const float* stats,
                       void* dq, void* dk, void* dv_out, float* dtable, void* workspace, size_t workspace_bytes,
                       int B, int heads, int Nq, int Nk, int kd, int dv, int n_offsets, int robust, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * PatchConvNet (ABI 17; patch_convnet.py).  Token-major rows [B*H*W, C]: row b*H*W + y*W + x is the reference's
+ * x.transpose(-1, -2).reshape(B, C, H, W) (patch_convnet.py:239-243), so the NCHW convolutions of Conv_blocks_se run on the GEMM's
+ * rows without a permuted copy.  C % 8 == 0 and bf16 row pointers 16-byte aligned everywhere.  Every reduction is a fixed-order
+ * sum of per-tile partials (no atomics): reruns are bit-identical.
+ *
+ * Depthwise 3x3 convolution, zero padding, stride 1 (Conv_blocks_se qkv_pos[2:4], patch_convnet.py:229-231):
+ *   nrv_dwconv3x3_fwd : d = bf16(gelu_erf(dwconv3x3(a) + bias)), a / d bf16 rows [B*H*W, C]; w fp32 [C, 9] (the Conv2d weight
+ *                       [C, 1, 3, 3] viewed flat); sq fp32 [B, C] = per-(sample, channel) sums of the fp32 d: the SE squeeze.
+ *   nrv_dwconv3x3_bwd : dd = (dg s[b] + dmean[b] / (H W)) gelu'(pre), pre recomputed from a (nine FMAs); da = the gather of dd
+ *                       through the taps, times the 1x1 conv's gelu' when gelu_stream is given (NRV_BF16 [rows, C] of
+ *                       NRV_EPI_BIAS_GELU, or NRV_U8 of NRV_EPI_BIAS_GELU_Q8 with C % 64 == 0; NULL: none), stored bf16 so that it
+ *                       feeds the 1x1 conv's TN / NT GEMMs directly.  dw fp32 [C, 9], db fp32 [C] (per-sample partials, then the
+ *                       samples in order).  workspace: nrv_dwconv3x3_bwd_workspace(B, H, W, C) bytes (fp32 dd and the partials).
+ *   B <= 65535, H * W <= 2^24; else NRV_ERR_SHAPE.
+ * Squeeze-and-excitation (utils.py:1148-1184), rd = round(C / 4) hidden units, C <= 4096, rd <= 1024, B <= 65535:
+ *   nrv_se_fwd   : mean = sq / HW; hid fp32 [B, rd] = relu(W_r mean + b_r) (kept for the backward); s fp32 [B, C] =
+ *                  sigmoid(W_e hid + b_e).  W_r fp32 [rd, C], W_e fp32 [C, rd] (the 1x1 Conv2d weights viewed flat).
+ *   nrv_se_apply : g = bf16(d s[b]): the A operand of the block's last 1x1 conv.  s 16-byte aligned.
+ *   nrv_se_bwd   : ds = sum over the H W rows of dg d (fixed order), dz = ds s (1 - s), dp = relu'(hid) W_e^T dz; dmean fp32
+ *                  [B, C] = W_r^T dp (the gradient of the mean, consumed by nrv_dwconv3x3_bwd); dW_e = sum_b dz hid^T,
+ *                  db_e = sum_b dz, dW_r = sum_b dp mean^T, db_r = sum_b dp, each over the samples in order.
+ *                  workspace: nrv_se_bwd_workspace(B, C, rd) bytes.
+ * LayerScale residual (patch_convnet.py:211-217, 262-265) with row-mode drop path, f = keep[r / rows_per_sample] / survival
+ * (keep fp32 [rows / rows_per_sample], optional: NULL means f = 1), C % 4 == 0, x / y / gamma / out 16-byte aligned:
+ *   nrv_ls_add_f32 : out = x + f gamma y (fp32 rows; out may alias x).
+ *   nrv_ls_bwd     : dz_bf16 = bf16(dy f gamma); dgamma = sum over rows of dy f y (per-128-row partials, then in order).
+ *                    workspace: nrv_ls_bwd_workspace(rows, C) bytes; rows <= 128 * 65535.
+ * nrv_dgelu_rows : out_bf16 = dx gelu'(stream), dx fp32 [rows, C], the stream as in nrv_dwconv3x3_bwd (the ConvStem's GELUs, whose
+ *                  derivative has to follow nrv_conv_fold).
+ * Class attention (Learned_Aggregation_Layer, patch_convnet.py:88-101): per (sample b, head h) one query q against Nk = 1 + Np
+ *   keys, S_j = scale q.k_j, P = softmax(S), o = sum_j P_j v_j; lse fp32 [B * heads] = log-sum-exp of S.  Key / value 0 is the
+ *   class row of sample b (kc / vc: row b), keys 1 .. Np are its patch rows (kp / vp: rows b*Np .. b*Np + Np - 1): the
+ *   cat((x_cls, x)) of patch_convnet.py:215 is never formed.  Head h of a row is columns h*dh .. h*dh + dh - 1; q, out: [B, ld].
+ *   Backward: dq (layout of q), dkc / dkp / dvc / dvp (layouts and leading dimensions of kc / kp / vc / vp) as bf16 from dout:
+ *   dS = P (dP - sum_j P_j dP_j), dP_j = dout.v_j.  Shapes: dh % 8 == 0, dh <= 1024, Nk <= 4096, every ld >= heads * dh and
+ *   % 8 == 0; else NRV_ERR_SHAPE.  kp / vp may be NULL when Np == 0.
+ * ---------------------------------------------------------------------------------------- */
+int nrv_dwconv3x3_fwd(const void* a, const float* w, const float* bias, void* d_bf16, float* sq,
+                      int B, int H, int W, int C, void* stream);
+size_t nrv_dwconv3x3_bwd_workspace(int B, int H, int W, int C);
+int nrv_dwconv3x3_bwd(const void* a, const float* w, const float* bias, const void* dg, const float* s, const float* dmean,
+                      const void* gelu_stream, int gelu_dtype, void* da_bf16, float* dw, float* db,
+                      void* workspace, size_t workspace_bytes, int B, int H, int W, int C, void* stream);
+int nrv_se_fwd(const float* sq, int HW, const float* wr, const float* br, const float* we, const float* be,
+               float* hid, float* s, int B, int C, int rd, void* stream);
+int nrv_se_apply(const void* d, const float* s, void* g_bf16, int B, int HW, int C, void* stream);
+size_t nrv_se_bwd_workspace(int B, int C, int rd);
+int nrv_se_bwd(const void* dg, const void* d, const float* sq, int HW, const float* s, const float* hid,
+               const float* wr, const float* we, float* dmean, float* dwr, float* dbr, float* dwe, float* dbe,
+               void* workspace, size_t workspace_bytes, int B, int C, int rd, void* stream);
+int nrv_ls_add_f32(const float* x, const float* y, const float* gamma, const float* keep, float survival, float* out,
+                   int64_t rows, int64_t rows_per_sample, int C, void* stream);
+size_t nrv_ls_bwd_workspace(int64_t rows, int C);
+int nrv_ls_bwd(const float* dy, const float* y, const float* gamma, const float* keep, float survival, void* dz_bf16,
+               float* dgamma, void* workspace, size_t workspace_bytes, int64_t rows, int64_t rows_per_sample, int C, void* stream);
+int nrv_dgelu_rows(const float* dx, const void* gelu_stream, int gelu_dtype, void* out_bf16, int64_t rows, int C, void* stream);
+int nrv_cls_attn_fwd(const void* q, int64_t ldq, const void* kc, int64_t ldkc, const void* kp, int64_t ldkp,
+                     const void* vc, int64_t ldvc, const void* vp, int64_t ldvp, void* out_bf16, int64_t ldo, float* lse,
+                     int B, int heads, int Np, int dh, float scale, void* stream);
+int nrv_cls_attn_bwd(const void* q, int64_t ldq, const void* kc, int64_t ldkc, const void* kp, int64_t ldkp,
+                     const void* vc, int64_t ldvc, const void* vp, int64_t ldvp, const void* dout_bf16, int64_t ldo,
+                     const float* lse, void* dq, void* dkc, void* dkp, void* dvc, void* dvp,
+                     int B, int heads, int Np, int dh, float scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Stand-alone SinkhornAttention(scores)  (the reference's exported module, utils.py:1025-1037, applied to a MATERIALISED

@@ -1142,3 +1142,201 @@ def bias_attn_bwd(q: Tensor, k: Tensor, v: Tensor, hq: int, hk: int, hv: int, ta
                                        int(bool(robust)), _stream()),
          "nrv_bias_attn_bwd")
     return dtable
+
+
+# ----------------------------------------------------------------------------------------------
+# PatchConvNet (ABI 17): depthwise 3x3, squeeze-and-excitation, LayerScale residuals, class attention
+# ----------------------------------------------------------------------------------------------
+def _gelu_stream(g: Optional[Tensor], rows: int, C: int) -> Tuple[Optional[int], int]:
+    """(pointer, dtype code) of a saved gelu' stream: bf16 [rows, C] (EPI_BIAS_GELU) or uint8 row pairs (EPI_BIAS_GELU_Q8)."""
+    if g is None:
+        return None, NRV_BF16
+    _dev(g, "gelu_stream")
+    if g.dtype == torch.uint8:
+        if C % 64 or g.numel() < (rows + 1) // 2 * 2 * C:
+            raise NrvError("the 8-bit gelu' stream is stored in row pairs: C % 64 == 0 and an even row count")
+        return g.data_ptr(), NRV_U8
+    _bf16(g, "gelu_stream")
+    if tuple(g.shape) != (rows, C) or not g.is_contiguous():
+        raise NrvError(f"gelu' stream must be contiguous [{rows}, {C}], got {tuple(g.shape)}")
+    return g.data_ptr(), NRV_BF16
+
+
+def _pcn_rows(a: Tensor, B: int, HW: int, C: int, name: str) -> None:
+    _bf16(a, name)
+    if not a.is_contiguous() or tuple(a.shape) != (B * HW, C):
+        raise NrvError(f"{name} must be contiguous bf16 [{B * HW}, {C}], got {tuple(a.shape)}")
+
+
+def dwconv3x3_fwd(a: Tensor, w: Tensor, bias: Tensor, B: int, H: int, W: int):
+    """(d bf16 [B*H*W, C] = gelu(dwconv3x3(a) + bias), sq fp32 [B, C] = per-sample channel sums of d)."""
+    C = a.shape[1]
+    _pcn_rows(a, B, H * W, C, "a"); _f32(w, "w"); _f32(bias, "bias")
+    w = w.reshape(C, 9).contiguous()
+    d = torch.empty_like(a)
+    sq = torch.empty(B, C, dtype=torch.float32, device=a.device)
+    _run("dwconv3x3_fwd", 18.0 * a.numel(), 4 * a.numel(),
+         lambda: _lib.load().nrv_dwconv3x3_fwd(a.data_ptr(), w.data_ptr(), bias.data_ptr(), d.data_ptr(), sq.data_ptr(), B, H, W, C,
+                                               _stream()), "nrv_dwconv3x3_fwd")
+    return d, sq
+
+
+def dwconv3x3_bwd(a: Tensor, w: Tensor, bias: Tensor, dg: Tensor, s: Tensor, dmean: Tensor, B: int, H: int, W: int,
+                  gelu_stream: Optional[Tensor] = None):
+    """(da bf16 [B*H*W, C] (times gelu_stream when given), dw fp32 [C, 1, 3, 3], db fp32 [C])."""
+    C = a.shape[1]
+    _pcn_rows(a, B, H * W, C, "a"); _pcn_rows(dg, B, H * W, C, "dg")
+    _f32(w, "w"); _f32(bias, "bias"); _f32(s, "s"); _f32(dmean, "dmean")
+    gp, gdt = _gelu_stream(gelu_stream, B * H * W, C)
+    w9 = w.reshape(C, 9).contiguous()
+    da = torch.empty_like(a)
+    dw = torch.empty(C, 9, dtype=torch.float32, device=a.device)
+    db = torch.empty(C, dtype=torch.float32, device=a.device)
+    lib = _lib.load()
+    ws = _workspace(lib.nrv_dwconv3x3_bwd_workspace(B, H, W, C), a.device)
+    _run("dwconv3x3_bwd", 54.0 * a.numel(), 18 * a.numel(),
+         lambda: lib.nrv_dwconv3x3_bwd(a.data_ptr(), w9.data_ptr(), bias.data_ptr(), dg.data_ptr(), s.data_ptr(), dmean.data_ptr(),
+                                       gp, gdt, da.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, C,
+                                       _stream()), "nrv_dwconv3x3_bwd")
+    return da, dw.reshape(C, 1, 3, 3), db
+
+
+def se_fwd(sq: Tensor, HW: int, wr: Tensor, br: Tensor, we: Tensor, be: Tensor):
+    """(s fp32 [B, C] = sigmoid(W_e relu(W_r sq / HW + b_r) + b_e), hid fp32 [B, rd])."""
+    _f32(sq, "sq")
+    B, C = sq.shape
+    rd = wr.shape[0]
+    for t, n in ((wr, "wr"), (br, "br"), (we, "we"), (be, "be")):
+        _f32(t, n)
+    wr2, we2 = wr.reshape(rd, C).contiguous(), we.reshape(C, rd).contiguous()
+    hid = torch.empty(B, rd, dtype=torch.float32, device=sq.device)
+    s = torch.empty(B, C, dtype=torch.float32, device=sq.device)
+    _run("se_fwd", 4.0 * B * C * rd, 8 * C * rd,
+         lambda: _lib.load().nrv_se_fwd(sq.data_ptr(), int(HW), wr2.data_ptr(), br.data_ptr(), we2.data_ptr(), be.data_ptr(),
+                                        hid.data_ptr(), s.data_ptr(), B, C, rd, _stream()), "nrv_se_fwd")
+    return s, hid
+
+
+def se_apply(d: Tensor, s: Tensor, HW: int) -> Tensor:
+    """g bf16 = d * s[sample] (SqueezeExcite's x * gate)."""
+    B, C = s.shape
+    _pcn_rows(d, B, HW, C, "d"); _f32(s, "s")
+    g = torch.empty_like(d)
+    _run("se_apply", 0.0, 4 * d.numel(),
+         lambda: _lib.load().nrv_se_apply(d.data_ptr(), s.data_ptr(), g.data_ptr(), B, int(HW), C, _stream()), "nrv_se_apply")
+    return g
+
+
+def se_bwd(dg: Tensor, d: Tensor, sq: Tensor, HW: int, s: Tensor, hid: Tensor, wr: Tensor, we: Tensor):
+    """(dmean fp32 [B, C], dW_r, db_r, dW_e, db_e) with the weight gradients in the Conv2d shapes of wr / we."""
+    B, C = s.shape
+    rd = hid.shape[1]
+    _pcn_rows(dg, B, HW, C, "dg"); _pcn_rows(d, B, HW, C, "d")
+    wr2, we2 = wr.reshape(rd, C).contiguous(), we.reshape(C, rd).contiguous()
+    dev = d.device
+    dmean = torch.empty(B, C, dtype=torch.float32, device=dev)
+    dwr = torch.empty(rd, C, dtype=torch.float32, device=dev)
+    dbr = torch.empty(rd, dtype=torch.float32, device=dev)
+    dwe = torch.empty(C, rd, dtype=torch.float32, device=dev)
+    dbe = torch.empty(C, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    ws = _workspace(lib.nrv_se_bwd_workspace(B, C, rd), dev)
+    _run("se_bwd", 2.0 * d.numel(), 4 * d.numel(),
+         lambda: lib.nrv_se_bwd(dg.data_ptr(), d.data_ptr(), sq.data_ptr(), int(HW), s.data_ptr(), hid.data_ptr(), wr2.data_ptr(),
+                                we2.data_ptr(), dmean.data_ptr(), dwr.data_ptr(), dbr.data_ptr(), dwe.data_ptr(), dbe.data_ptr(),
+                                ws.data_ptr(), ws.numel(), B, C, rd, _stream()), "nrv_se_bwd")
+    return dmean, dwr.reshape(wr.shape), dbr, dwe.reshape(we.shape), dbe
+
+
+def _ls_keep(keep: Optional[Tensor], rows: int) -> int:
+    if keep is None:
+        return 1
+    _f32(keep, "keep")
+    if keep.dim() != 1 or not keep.is_contiguous() or rows % keep.numel():
+        raise NrvError(f"LayerScale drop path: keep must be one value per sample, {keep.numel()} does not divide {rows} rows")
+    return rows // keep.numel()
+
+
+def ls_add(x: Tensor, y: Tensor, gamma: Tensor, keep: Optional[Tensor] = None, survival: float = 1.0,
+           out: Optional[Tensor] = None) -> Tensor:
+    """out fp32 = x + f * gamma * y, f = keep[sample] / survival (or 1)."""
+    _f32(x, "x"); _f32(y, "y"); _f32(gamma, "gamma")
+    if not x.is_contiguous() or y.shape != x.shape or not y.is_contiguous():
+        raise NrvError("ls_add: x and y must be contiguous fp32 [rows, C] of one shape")
+    rows, C = x.shape
+    per = _ls_keep(keep, rows)
+    o = torch.empty_like(x) if out is None else out
+    _run("ls_add", 0.0, 12 * x.numel(),
+         lambda: _lib.load().nrv_ls_add_f32(x.data_ptr(), y.data_ptr(), gamma.data_ptr(), _ptr(keep), float(survival), o.data_ptr(),
+                                            rows, per, C, _stream()), "nrv_ls_add_f32")
+    return o
+
+
+def ls_bwd(dy: Tensor, y: Tensor, gamma: Tensor, keep: Optional[Tensor] = None, survival: float = 1.0):
+    """(dz bf16 = dy * f * gamma, dgamma fp32 [C] = sum_rows dy * f * y)."""
+    _f32(dy, "dy"); _f32(y, "y"); _f32(gamma, "gamma")
+    if not dy.is_contiguous() or y.shape != dy.shape or not y.is_contiguous():
+        raise NrvError("ls_bwd: dy and y must be contiguous fp32 [rows, C] of one shape")
+    rows, C = dy.shape
+    per = _ls_keep(keep, rows)
+    dz = torch.empty(rows, C, dtype=torch.bfloat16, device=dy.device)
+    dgamma = torch.empty(C, dtype=torch.float32, device=dy.device)
+    lib = _lib.load()
+    ws = _workspace(lib.nrv_ls_bwd_workspace(rows, C), dy.device)
+    _run("ls_bwd", 0.0, 10 * dy.numel(),
+         lambda: lib.nrv_ls_bwd(dy.data_ptr(), y.data_ptr(), gamma.data_ptr(), _ptr(keep), float(survival), dz.data_ptr(),
+                                dgamma.data_ptr(), ws.data_ptr(), ws.numel(), rows, per, C, _stream()), "nrv_ls_bwd")
+    return dz, dgamma
+
+
+def dgelu_rows(dx: Tensor, gelu_stream: Tensor) -> Tensor:
+    """bf16(dx * gelu'), dx fp32 [rows, C], the stream as saved by EPI_BIAS_GELU (bf16) or EPI_BIAS_GELU_Q8 (uint8)."""
+    _f32(dx, "dx")
+    dx = dx.contiguous()
+    rows, C = dx.shape
+    gp, gdt = _gelu_stream(gelu_stream, rows, C)
+    out = torch.empty(rows, C, dtype=torch.bfloat16, device=dx.device)
+    _run("dgelu_rows", 0.0, 8 * dx.numel(),
+         lambda: _lib.load().nrv_dgelu_rows(dx.data_ptr(), gp, gdt, out.data_ptr(), rows, C, _stream()), "nrv_dgelu_rows")
+    return out
+
+
+def _ca_view(t: Optional[Tensor], rows: int, name: str) -> int:
+    if t is None:
+        return 0
+    _bf16(t, name)
+    if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] < rows:
+        raise NrvError(f"{name}: bf16 rows [>= {rows}, C] with contiguous columns, got {tuple(t.shape)} stride {t.stride()}")
+    return t.stride(0)
+
+
+def cls_attn_fwd(q: Tensor, kc: Tensor, kp: Optional[Tensor], vc: Tensor, vp: Optional[Tensor], B: int, heads: int, Np: int,
+                 dh: int, scale: float):
+    """(o bf16 [B, heads*dh], lse fp32 [B*heads]): one query per sample against the class key and its Np patch keys."""
+    lq, lkc, lvc = _ca_view(q, B, "q"), _ca_view(kc, B, "kc"), _ca_view(vc, B, "vc")
+    lkp, lvp = _ca_view(kp, B * Np, "kp"), _ca_view(vp, B * Np, "vp")
+    o = torch.empty(B, heads * dh, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(B * heads, dtype=torch.float32, device=q.device)
+    _run("cls_attn_fwd", 4.0 * B * heads * (Np + 1) * dh, 4 * B * (Np + 1) * heads * dh,
+         lambda: _lib.load().nrv_cls_attn_fwd(q.data_ptr(), lq, kc.data_ptr(), lkc, _ptr(kp), lkp, vc.data_ptr(), lvc, _ptr(vp), lvp,
+                                              o.data_ptr(), o.stride(0), lse.data_ptr(), B, heads, Np, dh, float(scale), _stream()),
+         "nrv_cls_attn_fwd")
+    return o, lse
+
+
+def cls_attn_bwd(q: Tensor, kc: Tensor, kp: Optional[Tensor], vc: Tensor, vp: Optional[Tensor], dout: Tensor, lse: Tensor,
+                 B: int, heads: int, Np: int, dh: int, scale: float):
+    """(dq, dkc, dkp, dvc, dvp), bf16, each shaped like its input."""
+    lq, lkc, lvc = _ca_view(q, B, "q"), _ca_view(kc, B, "kc"), _ca_view(vc, B, "vc")
+    lkp, lvp = _ca_view(kp, B * Np, "kp"), _ca_view(vp, B * Np, "vp")
+    _ca_view(dout, B, "dout"); _f32(lse, "lse")
+    # the kernel writes each gradient with its input's leading dimension: same strides
+    outs = [torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=t.device) if t is not None else None
+            for t in (q, kc, kp, vc, vp)]
+    dq, dkc, dkp, dvc, dvp = outs
+    _run("cls_attn_bwd", 8.0 * B * heads * (Np + 1) * dh, 8 * B * (Np + 1) * heads * dh,
+         lambda: _lib.load().nrv_cls_attn_bwd(q.data_ptr(), lq, kc.data_ptr(), lkc, _ptr(kp), lkp, vc.data_ptr(), lvc, _ptr(vp), lvp,
+                                              dout.data_ptr(), dout.stride(0), lse.data_ptr(), dq.data_ptr(), dkc.data_ptr(),
+                                              _ptr(dkp), dvc.data_ptr(), _ptr(dvp), B, heads, Np, dh, float(scale), _stream()),
+         "nrv_cls_attn_bwd")
+    return dq, dkc, dkp, dvc, dvp

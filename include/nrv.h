@@ -413,6 +413,32 @@ int nrv_sinkhorn_bwd(const float* scores, const float* dout, const float* lse, c
                      float* dscores, int64_t G, int R, int C, int iters, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Talking-heads attention on materialised matrices (added to ABI 17 without changing an existing prototype, so the version number stays; cait.py:107-120, CaiT's Attention): the scores of all heads are
+ * mixed by mix_heads_pre_attn before the normalisation and the weights by mix_heads_post_attn after it.  With S = q k^T * scale
+ * (nrv_bgemm), W1 = mix_heads_pre_attn, W2 = mix_heads_post_attn (fp32 [H, H], indexed [h, g]):
+ *     T[b,g] = sum_h W1[h,g] S[b,h]   (cait.py:107-109)     P = attend(T)   (:111)     A[b,g] = sum_h W2[h,g] P[b,h]   (:114-116)
+ * and A meets v in nrv_bgemm (:118).  All matrices [B, H, Nq, Nk] contiguous; S, P, dA, dS, in, dout, din fp32; A / out fp32 or
+ * bf16 (a_dtype / out_dtype).  1 <= H <= 16, Nq >= 1, 1 <= Nk <= 1025, no divisibility requirement; anything else returns
+ * NRV_ERR_SHAPE before a launch.  fp32 arithmetic; no atomics: the parameter gradients are sums of per-workgroup partials
+ * (workspace) added in index order by a second kernel, so reruns are bit-identical.
+ *   nrv_th_softmax_fwd   attend = softmax(dim = -1) in one pass: reads S once, writes P (kept for the backward) and A.
+ *   nrv_th_softmax_bwd   from dA (= dO v^T, nrv_bgemm), P, S: dS = W1-mix of dT, dT = P (dP - <P, dP>), dP = W2-mix of dA;
+ *                        dW2[h,g] = sum P[b,h,i,j] dA[b,g,i,j],  dW1[h,g] = sum S[b,h,i,j] dT[b,g,i,j]  (fp32 [H, H]).
+ *   nrv_head_mix_fwd     out[b,g] = sum_h W[h,g] in[b,h] alone.  robust=True (SinkhornAttention, utils.py:1025-1037, normalises rows
+ *                        AND columns, so it cannot be row-local): nrv_head_mix_fwd(W1) -> nrv_sinkhorn_fwd -> nrv_head_mix_fwd(W2).
+ *   nrv_head_mix_bwd     din[b,h] = sum_g W[h,g] dout[b,g];  dW[h,g] = sum in[b,h,i,j] dout[b,g,i,j].
+ * ---------------------------------------------------------------------------------------- */
+int nrv_th_softmax_fwd(const float* S, const float* W1, const float* W2, float* P, void* A, int a_dtype,
+                       int B, int H, int Nq, int Nk, void* stream);
+size_t nrv_th_softmax_bwd_workspace(int B, int H, int Nq, int Nk);
+int nrv_th_softmax_bwd(const float* dA, const float* P, const float* S, const float* W1, const float* W2, float* dS,
+                       float* dW1, float* dW2, void* workspace, size_t workspace_bytes, int B, int H, int Nq, int Nk, void* stream);
+int nrv_head_mix_fwd(const float* in, const float* W, void* out, int out_dtype, int B, int H, int Nq, int Nk, void* stream);
+size_t nrv_head_mix_bwd_workspace(int B, int H, int Nq, int Nk);
+int nrv_head_mix_bwd(const float* dout, const float* in, const float* W, float* din, float* dW, void* workspace,
+                     size_t workspace_bytes, int B, int H, int Nq, int Nk, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Batched small GEMM with arbitrary strides (bf16 MFMA, fp32 accumulation): for every (g1 < G1, g2 < G2)
  *   C[g1,g2][m,n] = alpha * sum_k A[g1,g2][m,k] * B[g1,g2][k,n],   element (g1, g2, row, col) of an operand at
  *   base + g1 * b1 + g2 * b2 + row * rs + col * cs  (ELEMENT strides; dtype fp32 or bf16 per operand; operands are rounded to

@@ -121,6 +121,14 @@ SIGNATURES = {
                                  c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "nrv_sinkhorn_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "nrv_sinkhorn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "nrv_th_softmax_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "nrv_th_softmax_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "nrv_th_softmax_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                   c_int, c_int, c_int, c_int, c_void_p]),
+    "nrv_head_mix_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "nrv_head_mix_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "nrv_head_mix_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int,
+                                 c_void_p]),
     "nrv_bgemm": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64,
                           c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "nrv_set_reserved_cus": (c_int, [c_int]),

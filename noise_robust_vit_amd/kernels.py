@@ -1340,3 +1340,86 @@ def cls_attn_bwd(q: Tensor, kc: Tensor, kp: Optional[Tensor], vc: Tensor, vp: Op
                                               _ptr(dkp), dvc.data_ptr(), _ptr(dvp), B, heads, Np, dh, float(scale), _stream()),
          "nrv_cls_attn_bwd")
     return dq, dkc, dkp, dvc, dvp
+
+
+# ---- talking-heads attention on materialised [B,H,Nq,Nk] matrices (CaiT, cait.py:107-120; include/nrv.h) ---------------
+TH_MAX_HEADS, TH_MAX_KEYS = 16, 1025
+
+
+def th_shape_ok(H: int, Nq: int, Nk: int) -> bool:
+    """The range of the talking-heads kernels (include/nrv.h): 1 <= H <= 16, Nq >= 1, 1 <= Nk <= 1025."""
+    return 1 <= H <= TH_MAX_HEADS and Nq >= 1 and 1 <= Nk <= TH_MAX_KEYS
+
+
+def _th_args(t: Tensor, W: Tuple[Tensor, ...], name: str) -> Tuple[int, int, int, int]:
+    _f32(t, name)
+    if t.dim() != 4 or not t.is_contiguous():
+        raise NrvError(f"{name} must be a contiguous fp32 [B, H, Nq, Nk] matrix, got {tuple(t.shape)}")
+    B, H, Nq, Nk = t.shape
+    for w in W:
+        _f32(w, "mixing matrix")
+        if tuple(w.shape) != (H, H) or not w.is_contiguous():
+            raise NrvError(f"the head-mixing matrix must be contiguous fp32 [{H}, {H}], got {tuple(w.shape)}")
+    if not th_shape_ok(H, Nq, Nk):
+        raise NotImplementedError(f"talking-heads kernels: {H} heads, {Nq} x {Nk} scores; they take at most {TH_MAX_HEADS} heads and "
+                                  f"{TH_MAX_KEYS} keys")
+    return B, H, Nq, Nk
+
+
+def _th_like(t: Tensor, other: Tensor, name: str) -> None:
+    _f32(other, name)
+    if other.shape != t.shape or not other.is_contiguous():
+        raise NrvError(f"{name} must be contiguous fp32 of shape {tuple(t.shape)}, got {tuple(other.shape)}")
+
+
+def th_softmax_fwd(S: Tensor, W1: Tensor, W2: Tensor, a_dtype: torch.dtype = torch.bfloat16):
+    """(P fp32, A): T = W1-mix of S, P = softmax(T, -1), A = W2-mix of P (cait.py:107-116)."""
+    B, H, Nq, Nk = _th_args(S, (W1, W2), "S")
+    P = torch.empty_like(S)
+    A = torch.empty(S.shape, dtype=a_dtype, device=S.device)
+    lib = _lib.load()
+    _run("talking_heads_fwd", 2.0 * 2 * H * S.numel(), S.numel() * (8 + A.element_size()),
+         lambda: lib.nrv_th_softmax_fwd(S.data_ptr(), W1.data_ptr(), W2.data_ptr(), P.data_ptr(), A.data_ptr(), _dt(A, "A"),
+                                        B, H, Nq, Nk, _stream()), "nrv_th_softmax_fwd")
+    return P, A
+
+
+def th_softmax_bwd(dA: Tensor, P: Tensor, S: Tensor, W1: Tensor, W2: Tensor):
+    """(dS fp32, dW1, dW2) of th_softmax_fwd from dA fp32 (= dO v^T)."""
+    B, H, Nq, Nk = _th_args(S, (W1, W2), "S")
+    _th_like(S, dA, "dA"); _th_like(S, P, "P")
+    dS = torch.empty_like(S)
+    dW1 = torch.empty(H, H, dtype=torch.float32, device=S.device)
+    dW2 = torch.empty(H, H, dtype=torch.float32, device=S.device)
+    lib = _lib.load()
+    ws = _workspace(lib.nrv_th_softmax_bwd_workspace(B, H, Nq, Nk), S.device)
+    _run("talking_heads_bwd", 2.0 * 4 * H * S.numel(), S.numel() * 16,
+         lambda: lib.nrv_th_softmax_bwd(dA.data_ptr(), P.data_ptr(), S.data_ptr(), W1.data_ptr(), W2.data_ptr(), dS.data_ptr(),
+                                        dW1.data_ptr(), dW2.data_ptr(), ws.data_ptr(), ws.numel(), B, H, Nq, Nk, _stream()),
+         "nrv_th_softmax_bwd")
+    return dS, dW1, dW2
+
+
+def head_mix_fwd(x: Tensor, W: Tensor, out_dtype: torch.dtype = torch.float32) -> Tensor:
+    """out[b,g] = sum_h W[h,g] x[b,h] (einsum 'b h i j, h g -> b g i j', cait.py:107-109, 114-116)."""
+    B, H, Nq, Nk = _th_args(x, (W,), "x")
+    out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    lib = _lib.load()
+    _run("head_mix_fwd", 2.0 * H * x.numel(), x.numel() * (4 + out.element_size()),
+         lambda: lib.nrv_head_mix_fwd(x.data_ptr(), W.data_ptr(), out.data_ptr(), _dt(out, "out"), B, H, Nq, Nk, _stream()),
+         "nrv_head_mix_fwd")
+    return out
+
+
+def head_mix_bwd(dout: Tensor, x: Tensor, W: Tensor):
+    """(din fp32, dW fp32 [H, H]) of head_mix_fwd."""
+    B, H, Nq, Nk = _th_args(x, (W,), "x")
+    _th_like(x, dout, "dout")
+    din = torch.empty_like(x)
+    dW = torch.empty(H, H, dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    ws = _workspace(lib.nrv_head_mix_bwd_workspace(B, H, Nq, Nk), x.device)
+    _run("head_mix_bwd", 2.0 * 2 * H * x.numel(), x.numel() * 12,
+         lambda: lib.nrv_head_mix_bwd(dout.data_ptr(), x.data_ptr(), W.data_ptr(), din.data_ptr(), dW.data_ptr(), ws.data_ptr(),
+                                      ws.numel(), B, H, Nq, Nk, _stream()), "nrv_head_mix_bwd")
+    return din, dW

@@ -191,6 +191,8 @@ class Trainer:
             raise RuntimeError("Trainer.capture: CutMix draws its box on the host every step and cannot be replayed")
         if self.reducer is not None and (self.reducer.world > 1 or self.reducer.force):
             raise RuntimeError("Trainer.capture: collectives are not captured; use the eager step with a process group")
+        if any(getattr(m, "layer_dropout", 0.0) > 0 for m in self.model.modules()):
+            raise RuntimeError("Trainer.capture: layer_dropout draws the kept layers on the host every step; a graph would freeze one draw")
         opt = self.opt
         saved = (opt.param.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone(), opt.step_count, self.step_idx)
         buffers = [(b, b.clone()) for b in self.model.buffers()]      # batch-norm running statistics move in the warm-up steps

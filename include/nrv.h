@@ -526,6 +526,47 @@ int nrv_adamw_f32(float* p, const void* grad, int grad_dtype, float* m, float* v
                   double lr, double beta1, double beta2, double eps, double weight_decay, int step,
                   const float* gnorm_sq, float max_norm, const float* step_scalars, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Tokens-to-token pieces (T2T-ViT, t2t.py:58-93; added to ABI 17, no existing prototype changed).
+ *   nrv_soft_split_fwd: nn.Unfold(ks, stride, pad) on token-major rows.  src = NCHW image (NRV_SPLIT_NCHW, fp32|bf16; ld_src
+ *                    ignored) or bf16 token rows [B*H*W, ld_src] (NRV_SPLIT_ROWS, ld_src >= C: RearrangeImage is the
+ *                    addressing) -> cols bf16 [B*Ho*Wo, KP], feature c*ks*ks + ky*ks + kx (nn.Unfold's order; nrv_conv_unfold
+ *                    writes (ky, kx, c)), KP = ks*ks*C rounded up to 8.  Taps outside the image and columns >= ks*ks*C are
+ *                    zeros.  A copy: bf16 sources arrive bit-exact, fp32 ones rounded to nearest even.
+ *   nrv_soft_split_bwd: its input gradient, a fold in gather form: dx fp32 rows [B*H*W, ld_dx] (ld_dx >= C; columns >= C
+ *                    are written as zeros) from dcols bf16 [B*Ho*Wo, KP].  Each element sums the at most ceil(ks / stride)^2
+ *                    windows that cover it, ky then kx ascending: no scatter, no atomics, reruns are bit-identical.
+ *   Ho = (H + 2 pad - ks) / stride + 1; ks <= 7, pad < ks; else NRV_ERR_SHAPE.  cols 16-byte aligned.
+ *   nrv_layernorm_pad_fwd / _bwd: nn.LayerNorm over the first n columns of rows stored with stride ld (n <= 4096, ld >= n,
+ *                    ld % 8 == 0, ld <= 2^20; else NRV_ERR_SHAPE): statistics over n, gamma / beta / dgamma / dbeta fp32 [n],
+ *                    columns n .. ld - 1 of y / dx written as zeros (the zero pad columns of odd feature widths: 147 in 152,
+ *                    1323 in 1328).  Otherwise the arguments of nrv_layernorm_fwd / _bwd; dgamma / dbeta are per-slab column
+ *                    sums added in slab order (deterministic).  workspace: nrv_layernorm_pad_bwd_workspace(rows, n) bytes.
+ *   nrv_attn_wide_fwd / _bwd: the streaming softmax attention of nrv_attn_fwd / _bwd (same tensors, online softmax over
+ *                    64-key tiles, LSE saved, P recomputed in the backward, no atomics) for head dims 128 < dh <= 192 with
+ *                    dh % 8 == 0 and any N: the [N, N] matrix is never written.  The upper limit is the 64 KB of static
+ *                    LDS (two [64][192] bf16 tiles + statistics = 49 664 bytes; 256 columns would need 66 048).  Anything
+ *                    else returns NRV_ERR_SHAPE before a launch; wider heads run the composed path (nrv_bgemm +
+ *                    nrv_sinkhorn_fwd with 0 iterations).  delta_ws: fp32 [B*H*N] scratch.
+ * ---------------------------------------------------------------------------------------- */
+#define NRV_SPLIT_NCHW 0
+#define NRV_SPLIT_ROWS 1
+int nrv_soft_split_fwd(const void* src, int src_dtype, int src_layout, int64_t ld_src, void* cols_bf16,
+                       int B, int C, int H, int W, int ks, int stride, int pad, void* stream);
+int nrv_soft_split_bwd(const void* dcols_bf16, float* dx, int64_t ld_dx, int B, int C, int H, int W, int ks, int stride,
+                       int pad, void* stream);
+int nrv_layernorm_pad_fwd(const void* x, int x_dtype, const float* gamma, const float* beta, void* y_bf16, float* mean,
+                          float* rstd, int64_t rows, int n, int64_t ld, float eps, void* stream);
+size_t nrv_layernorm_pad_bwd_workspace(int64_t rows, int n);
+int nrv_layernorm_pad_bwd(const void* dy_bf16, const void* x, int x_dtype, const float* gamma, const float* mean,
+                          const float* rstd, const void* dres, int dres_dtype, float* dx_f32, void* dx_bf16,
+                          float* dgamma, float* dbeta, int accumulate, void* workspace, size_t workspace_bytes,
+                          int64_t rows, int n, int64_t ld, void* stream);
+int nrv_attn_wide_fwd(const void* qkv_bf16, void* out_bf16, float* lse, int B, int N, int H, int dh, float scale,
+                      void* stream);
+int nrv_attn_wide_bwd(const void* qkv_bf16, const void* out_bf16, const void* dout_bf16, const float* lse,
+                      void* dqkv_bf16, float* delta_ws, int B, int N, int H, int dh, float scale, void* stream);
+
 /* CUs the GEMM launches leave free (process-wide; default 0; returns the previous value, or a negative error code when n is
  * negative or leaves fewer than 8 CUs).  The NT GEMM is persistent (one workgroup per CU for the whole launch) and the TN
  * GEMM sizes its token splits to one round of the CUs: with a collective's kernels resident on some CUs (RCCL all-reduce

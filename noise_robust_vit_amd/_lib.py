@@ -21,6 +21,7 @@ PATCH_P1P2C, PATCH_CP1P2 = 0, 1
 ABI_VERSION = 17
 ATTN_QKV_BLOCKED, ATTN_OUT_BLOCKED = 1, 2      # include/nrv.h: NRV_ATTN_*_BLOCKED
 CONV_NCHW, CONV_NHWC = 0, 1                    # include/nrv.h: NRV_CONV_*
+SPLIT_NCHW, SPLIT_ROWS = 0, 1                  # include/nrv.h: NRV_SPLIT_*
 
 
 
@@ -129,6 +130,16 @@ SIGNATURES = {
     "nrv_head_mix_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "nrv_head_mix_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int,
                                  c_void_p]),
+    "nrv_soft_split_fwd": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "nrv_soft_split_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "nrv_layernorm_pad_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int64, c_int, c_int64, c_float, c_void_p]),
+    "nrv_layernorm_pad_bwd_workspace": (c_size_t, [c_int64, c_int]),
+    "nrv_layernorm_pad_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int64, c_int, c_int64, c_void_p]),
+    "nrv_attn_wide_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "nrv_attn_wide_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                                  c_void_p]),
     "nrv_bgemm": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64,
                           c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "nrv_set_reserved_cus": (c_int, [c_int]),

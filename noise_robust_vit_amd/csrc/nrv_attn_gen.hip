@@ -70,8 +70,8 @@ constexpr float MASKED = -FLT_MAX;
 template <int KS>
 struct GenCfg {
     static constexpr int DHP = 32 * KS, RB = 2 * DHP, TILE = GT * RB, DT = DHP / 16;
-    static constexpr int UNITS = RB / 32;                                  // 2, 4, 6, 8
-    static constexpr int UM = UNITS == 2 ? 1 : UNITS == 4 ? 3 : UNITS == 6 ? 1 : 7;   // XOR mask that stays inside a row
+    static constexpr int UNITS = RB / 32;                                  // 2, 4, 6, 8; wide heads: 10, 12
+    static constexpr int UM = UNITS == 2 ? 1 : UNITS == 4 ? 3 : UNITS == 6 ? 1 : UNITS == 10 ? 1 : UNITS == 12 ? 3 : 7;   // XOR mask that stays inside a row
 };
 
 template <int KS>
@@ -732,6 +732,46 @@ extern "C" int nrv_attn_mem_bwd(const void* qkv_bf16, const void* out_bf16, cons
     hipLaunchKernelGGL(mem_batch_sum_kernel, dim3(gx, 1u), dim3(256), 0, s, dmem_f32, dmem_sum_f32, n4, n4 * MEM_SUM_GROUP, groups, groups);
     NRV_CHECK_LAUNCH();
     return 0;
+}
+
+// Wide single-head-style attention (T2T-ViT's stage transformers, t2t.py:76-83: heads = 1, dim_head = 147 stored as 152): the
+// MEM = false instantiation at KS = 5 / 6, i.e. 128 < dh <= 192 with dh % 8 == 0.  The limit is the 64 KB of static LDS: the
+// key-owner pass holds two [64][32 KS] bf16 tiles and 512 bytes of statistics, 49 664 bytes at KS = 6 and over 64 KB at KS = 8.
+static int wide_ks(int dh) { return (dh & 7) || dh <= 128 || dh > 192 ? 0 : dh <= 160 ? 5 : 6; }
+static int wide_args(int B, int N, int H, int dh) {
+    if (B <= 0 || N <= 0 || H <= 0 || wide_ks(dh) == 0) return NRV_ERR_SHAPE;
+    if ((long long)N > 0x7fffffffll - GT || (long long)B * H * ((N + GT - 1) / GT) > 0x7fffffffll) return NRV_ERR_SHAPE;
+    if ((long long)N * 3 * H * dh > 0x7fffffffll) return NRV_ERR_SHAPE;
+    return 0;
+}
+
+extern "C" int nrv_attn_wide_fwd(const void* qkv_bf16, void* out_bf16, float* lse, int B, int N, int H, int dh, float scale,
+                                 void* stream) {
+    if (int rc = wide_args(B, N, H, dh)) return rc;
+    if (!qkv_bf16 || !out_bf16 || !lse) return NRV_ERR_NULL;
+    if (!nrv_aligned16(qkv_bf16) || !nrv_aligned16(out_bf16) || !aligned4(lse)) return NRV_ERR_ALIGN;
+    GenParams p = make_params(qkv_bf16, nullptr, 0, 0, nullptr, 0, 0, B, N, H, dh, scale);
+    p.o = static_cast<bf16_t*>(out_bf16);
+    p.lse = lse;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return wide_ks(dh) == 5 ? launch<5, false>(p, false, s) : launch<6, false>(p, false, s);
+}
+
+extern "C" int nrv_attn_wide_bwd(const void* qkv_bf16, const void* out_bf16, const void* dout_bf16, const float* lse,
+                                 void* dqkv_bf16, float* delta_ws, int B, int N, int H, int dh, float scale, void* stream) {
+    if (int rc = wide_args(B, N, H, dh)) return rc;
+    if (!qkv_bf16 || !out_bf16 || !dout_bf16 || !lse || !dqkv_bf16 || !delta_ws) return NRV_ERR_NULL;
+    if (!nrv_aligned16(qkv_bf16) || !nrv_aligned16(out_bf16) || !nrv_aligned16(dout_bf16) || !nrv_aligned16(dqkv_bf16) ||
+        !aligned4(lse) || !aligned4(delta_ws))
+        return NRV_ERR_ALIGN;
+    GenParams p = make_params(qkv_bf16, nullptr, 0, 0, nullptr, 0, 0, B, N, H, dh, scale);
+    p.out = static_cast<const bf16_t*>(out_bf16);
+    p.dout = static_cast<const bf16_t*>(dout_bf16);
+    p.dqkv = static_cast<bf16_t*>(dqkv_bf16);
+    p.lse = const_cast<float*>(lse);
+    p.delta = delta_ws;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return wide_ks(dh) == 5 ? launch<5, false>(p, true, s) : launch<6, false>(p, true, s);
 }
 
 extern "C" int nrv_mask_pack_bits(const void* mask_u8, uint32_t* bits, int64_t rows, int cols, void* stream) {

@@ -1,0 +1,302 @@
+// Tokens-to-token (T2T-ViT, t2t.py:58-93) pieces that the ViT kernels do not cover:
+//   soft split : nn.Unfold(ks, stride, pad) on token-major rows.  src = NCHW image (fp32 | bf16) or bf16 token rows
+//                [B*H*W, ld_src] (the 'b (h w) c -> b c h w' of RearrangeImage is the addressing) -> cols bf16 [B*Ho*Wo, KP],
+//                feature c*ks*ks + ky*ks + kx (nn.Unfold's channel-major order), KP = ks*ks*C rounded up to 8; taps outside
+//                the image and columns >= ks*ks*C are zero.  One thread = 8 consecutive output features, one 16-byte store.
+//   its backward: a fold in gather form.  dx[(b, y, x), c] = sum over the windows (oy, ox) that cover (y, x) of
+//                dcols[(b, oy, ox), c*ks*ks + ky*ks + kx], ky then kx ascending: at most ceil(ks / stride)^2 terms in a fixed
+//                order, fp32, no scatter, no atomics.  Columns C .. ld_dx - 1 of dx are written as zeros.
+//   LayerNorm over the true width n of rows stored with a stride ld >= n (n = 147, 1323: ks*ks*C is no multiple of 8, the
+//                GEMMs need K % 8 == 0, so the residual stream keeps zero pad columns): statistics over n, pad columns of
+//                y / dx written as zeros.  One wave per row, two passes over the row for mean and centred variance (the
+//                second pass hits L1 / L2).  dgamma / dbeta: per-slab column sums, then a finalize in slab order.
+#include "nrv_common.hpp"
+
+namespace {
+
+struct SplitGeom {
+    int B, C, H, W, Ho, Wo, ks, stride, pad, KP;
+    long long ld;            // row stride of the token-row source (forward) / of dx (backward)
+};
+
+template <int SRC>      // 0: NCHW fp32, 1: NCHW bf16, 2: bf16 token rows [B*H*W, ld]
+__device__ __forceinline__ bf16_t split_src(const void* src, const SplitGeom& g, int b, int c, int iy, int ix) {
+    if (SRC == 0) return f32_to_bf16(reinterpret_cast<const float*>(src)[(((long long)b * g.C + c) * g.H + iy) * g.W + ix]);
+    if (SRC == 1) return reinterpret_cast<const bf16_t*>(src)[(((long long)b * g.C + c) * g.H + iy) * g.W + ix];
+    return reinterpret_cast<const bf16_t*>(src)[(((long long)b * g.H + iy) * g.W + ix) * g.ld + c];
+}
+
+template <int SRC>
+__global__ __launch_bounds__(256) void soft_split_kernel(const void* __restrict__ src, bf16_t* __restrict__ out, SplitGeom g) {
+    const int kk = g.ks * g.ks, F = kk * g.C, F8 = g.KP >> 3;
+    const long long total = (long long)g.B * g.Ho * g.Wo * F8;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long t = i / F8;
+        const int f0 = (int)(i - t * F8) * 8;
+        const int b = (int)(t / ((long long)g.Ho * g.Wo));
+        const int rem = (int)(t - (long long)b * g.Ho * g.Wo);
+        const int oy = rem / g.Wo, ox = rem - (rem / g.Wo) * g.Wo;
+        unsigned v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int f = f0 + j;
+            const int c = f / kk, k = f - c * kk;
+            const int ky = k / g.ks, kx = k - ky * g.ks;
+            const int iy = oy * g.stride - g.pad + ky, ix = ox * g.stride - g.pad + kx;
+            v[j] = (f < F && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W) ? split_src<SRC>(src, g, b, c, iy, ix) : 0u;
+        }
+        u32x4_t pk = {v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)};
+        *reinterpret_cast<u32x4_t*>(out + t * g.KP + f0) = pk;
+    }
+}
+
+__global__ __launch_bounds__(256) void soft_split_bwd_kernel(const bf16_t* __restrict__ dcols, float* __restrict__ dx, SplitGeom g) {
+    const int kk = g.ks * g.ks;
+    const long long total = (long long)g.B * g.H * g.W * g.ld;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long pix = i / g.ld;
+        const int c = (int)(i - pix * g.ld);
+        float acc = 0.f;
+        if (c < g.C) {
+            const int b = (int)(pix / ((long long)g.H * g.W));
+            const int rem = (int)(pix - (long long)b * g.H * g.W);
+            const int y = rem / g.W, x = rem - (rem / g.W) * g.W;
+            for (int ky = 0; ky < g.ks; ++ky) {
+                const int ny = y + g.pad - ky;
+                if (ny < 0 || ny % g.stride) continue;
+                const int oy = ny / g.stride;
+                if (oy >= g.Ho) continue;
+                for (int kx = 0; kx < g.ks; ++kx) {
+                    const int nx = x + g.pad - kx;
+                    if (nx < 0 || nx % g.stride) continue;
+                    const int ox = nx / g.stride;
+                    if (ox >= g.Wo) continue;
+                    acc += bf16_to_f32(dcols[(((long long)b * g.Ho + oy) * g.Wo + ox) * g.KP + c * kk + ky * g.ks + kx]);
+                }
+            }
+        }
+        dx[i] = acc;
+    }
+}
+
+int grid_for(long long work_items, int block, int cap) {
+    long long g = (work_items + block - 1) / block;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+
+int split_geom(SplitGeom& g, int B, int C, int H, int W, int ks, int stride, int pad, long long ld) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ks <= 0 || ks > 7 || stride <= 0 || pad < 0 || pad >= ks) return NRV_ERR_SHAPE;
+    if (H + 2 * pad < ks || W + 2 * pad < ks) return NRV_ERR_SHAPE;
+    g.B = B; g.C = C; g.H = H; g.W = W; g.ks = ks; g.stride = stride; g.pad = pad; g.ld = ld;
+    g.Ho = (H + 2 * pad - ks) / stride + 1;
+    g.Wo = (W + 2 * pad - ks) / stride + 1;
+    g.KP = (ks * ks * C + 7) & ~7;
+    if ((long long)B * g.Ho * g.Wo * g.KP > (1ll << 40) || (long long)B * H * W * (ld > C ? ld : C) > (1ll << 40)) return NRV_ERR_SHAPE;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// LayerNorm over n of ld columns
+// ---------------------------------------------------------------------------------------------
+constexpr int LNP_THREADS = 256;
+constexpr int LNP_WAVES = LNP_THREADS / 64;
+constexpr int LNP_MAX_N = 4096;
+constexpr int LNP_MAX_SLABS = 128;
+constexpr int LNP_SLAB_ROWS = 128;       // a slab holds at least this many rows (fewer slabs on short inputs)
+
+template <bool F32>
+__device__ __forceinline__ float ld1(const void* base, long long idx) {
+    if (F32) return reinterpret_cast<const float*>(base)[idx];
+    return bf16_to_f32(reinterpret_cast<const bf16_t*>(base)[idx]);
+}
+
+template <bool X_F32>
+__global__ __launch_bounds__(LNP_THREADS) void ln_pad_fwd_kernel(const void* __restrict__ x, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, bf16_t* __restrict__ y,
+                                                                 float* __restrict__ mean, float* __restrict__ rstd,
+                                                                 long long rows, int n, int ld, float eps) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float inv_n = 1.0f / (float)n;
+    for (long long r = (long long)blockIdx.x * LNP_WAVES + wave; r < rows; r += (long long)gridDim.x * LNP_WAVES) {
+        const long long base = r * ld;
+        float s = 0.f;
+        for (int j = lane; j < n; j += 64) s += ld1<X_F32>(x, base + j);
+        const float mu = wave_sum(s) * inv_n;
+        float q = 0.f;
+        for (int j = lane; j < n; j += 64) {
+            const float d = ld1<X_F32>(x, base + j) - mu;
+            q = fmaf(d, d, q);
+        }
+        const float rs = rsqrtf(wave_sum(q) * inv_n + eps);
+        for (int j = lane; j < ld; j += 64)
+            y[base + j] = j < n ? f32_to_bf16(fmaf((ld1<X_F32>(x, base + j) - mu) * rs, gamma[j], beta[j])) : (bf16_t)0;
+        if (lane == 0) {
+            mean[r] = mu;
+            rstd[r] = rs;
+        }
+    }
+}
+
+// dx = dres + rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * gamma, means over the n true columns
+template <bool X_F32, bool R_F32>
+__global__ __launch_bounds__(LNP_THREADS) void ln_pad_bwd_kernel(const bf16_t* __restrict__ dy, const void* __restrict__ x,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                                 const float* __restrict__ rstd, const void* __restrict__ dres,
+                                                                 float* __restrict__ dx32, bf16_t* __restrict__ dx16,
+                                                                 long long rows, int n, int ld) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float inv_n = 1.0f / (float)n;
+    for (long long r = (long long)blockIdx.x * LNP_WAVES + wave; r < rows; r += (long long)gridDim.x * LNP_WAVES) {
+        const long long base = r * ld;
+        const float mu = mean[r], rs = rstd[r];
+        float a = 0.f, b = 0.f;
+        for (int j = lane; j < n; j += 64) {
+            const float g = bf16_to_f32(dy[base + j]) * gamma[j];
+            const float xh = (ld1<X_F32>(x, base + j) - mu) * rs;
+            a += g;
+            b = fmaf(g, xh, b);
+        }
+        const float c1 = wave_sum(a) * inv_n, c2 = wave_sum(b) * inv_n;
+        for (int j = lane; j < ld; j += 64) {
+            float v = 0.f;
+            if (j < n) {
+                const float g = bf16_to_f32(dy[base + j]) * gamma[j];
+                const float xh = (ld1<X_F32>(x, base + j) - mu) * rs;
+                v = rs * (g - c1 - xh * c2);
+                if (dres) v += ld1<R_F32>(dres, base + j);
+            }
+            if (dx32) dx32[base + j] = v;
+            if (dx16) dx16[base + j] = f32_to_bf16(v);
+        }
+    }
+}
+
+// slab s sums rows [s * per, (s + 1) * per) of dy * xhat and dy for the columns of its block: part[s][0 | 1][n]
+template <bool X_F32>
+__global__ __launch_bounds__(LNP_THREADS) void ln_pad_dgb_partial_kernel(const bf16_t* __restrict__ dy, const void* __restrict__ x,
+                                                                         const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                         float* __restrict__ part, long long rows, long long per, int n, int ld) {
+    const int j = blockIdx.x * LNP_THREADS + threadIdx.x;
+    const int s = blockIdx.y;
+    if (j >= n) return;
+    const long long r0 = (long long)s * per;
+    const long long r1 = r0 + per < rows ? r0 + per : rows;
+    float dg = 0.f, db = 0.f;
+    for (long long r = r0; r < r1; ++r) {
+        const float d = bf16_to_f32(dy[r * ld + j]);
+        dg = fmaf(d, (ld1<X_F32>(x, r * ld + j) - mean[r]) * rstd[r], dg);
+        db += d;
+    }
+    part[((long long)s * 2 + 0) * n + j] = dg;
+    part[((long long)s * 2 + 1) * n + j] = db;
+}
+
+__global__ __launch_bounds__(LNP_THREADS) void ln_pad_dgb_final_kernel(const float* __restrict__ part, float* __restrict__ dgamma,
+                                                                       float* __restrict__ dbeta, int slabs, int n, int accumulate) {
+    const int j = blockIdx.x * LNP_THREADS + threadIdx.x;
+    if (j >= n) return;
+    float dg = 0.f, db = 0.f;
+    for (int s = 0; s < slabs; ++s) {
+        dg += part[((long long)s * 2 + 0) * n + j];
+        db += part[((long long)s * 2 + 1) * n + j];
+    }
+    dgamma[j] = accumulate ? dgamma[j] + dg : dg;
+    dbeta[j] = accumulate ? dbeta[j] + db : db;
+}
+
+int lnp_slabs(long long rows) {
+    long long s = (rows + LNP_SLAB_ROWS - 1) / LNP_SLAB_ROWS;
+    if (s > LNP_MAX_SLABS) s = LNP_MAX_SLABS;
+    return s < 1 ? 1 : (int)s;
+}
+
+int lnp_shape(long long rows, int n, long long ld) {
+    if (rows <= 0 || n <= 0 || n > LNP_MAX_N || ld < n || (ld & 7) || ld > (1 << 20)) return NRV_ERR_SHAPE;
+    if (rows * ld > (1ll << 40)) return NRV_ERR_SHAPE;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int nrv_soft_split_fwd(const void* src, int src_dtype, int src_layout, int64_t ld_src, void* cols_bf16,
+                                  int B, int C, int H, int W, int ks, int stride, int pad, void* stream) {
+    SplitGeom g{};
+    if (split_geom(g, B, C, H, W, ks, stride, pad, ld_src)) return NRV_ERR_SHAPE;
+    if (src_layout != NRV_SPLIT_NCHW && src_layout != NRV_SPLIT_ROWS) return NRV_ERR_SHAPE;
+    if (src_layout == NRV_SPLIT_ROWS && ld_src < C) return NRV_ERR_SHAPE;
+    if (!src || !cols_bf16) return NRV_ERR_NULL;
+    if (src_dtype != NRV_F32 && src_dtype != NRV_BF16) return NRV_ERR_DTYPE;
+    if (src_layout == NRV_SPLIT_ROWS && src_dtype != NRV_BF16) return NRV_ERR_DTYPE;
+    if (!nrv_aligned16(cols_bf16)) return NRV_ERR_ALIGN;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int grid = grid_for((long long)B * g.Ho * g.Wo * (g.KP >> 3), 256, 16384);
+    bf16_t* out = static_cast<bf16_t*>(cols_bf16);
+    if (src_layout == NRV_SPLIT_ROWS) hipLaunchKernelGGL((soft_split_kernel<2>), dim3(grid), dim3(256), 0, s, src, out, g);
+    else if (src_dtype == NRV_F32) hipLaunchKernelGGL((soft_split_kernel<0>), dim3(grid), dim3(256), 0, s, src, out, g);
+    else hipLaunchKernelGGL((soft_split_kernel<1>), dim3(grid), dim3(256), 0, s, src, out, g);
+    NRV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nrv_soft_split_bwd(const void* dcols_bf16, float* dx, int64_t ld_dx, int B, int C, int H, int W, int ks, int stride,
+                                  int pad, void* stream) {
+    SplitGeom g{};
+    if (split_geom(g, B, C, H, W, ks, stride, pad, ld_dx)) return NRV_ERR_SHAPE;
+    if (ld_dx < C) return NRV_ERR_SHAPE;
+    if (!dcols_bf16 || !dx) return NRV_ERR_NULL;
+    hipLaunchKernelGGL(soft_split_bwd_kernel, dim3(grid_for((long long)B * H * W * ld_dx, 256, 16384)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(dcols_bf16), dx, g);
+    NRV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nrv_layernorm_pad_fwd(const void* x, int x_dtype, const float* gamma, const float* beta, void* y_bf16, float* mean,
+                                     float* rstd, int64_t rows, int n, int64_t ld, float eps, void* stream) {
+    if (lnp_shape(rows, n, ld)) return NRV_ERR_SHAPE;
+    if (!x || !gamma || !beta || !y_bf16 || !mean || !rstd) return NRV_ERR_NULL;
+    if (x_dtype != NRV_F32 && x_dtype != NRV_BF16) return NRV_ERR_DTYPE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int grid = grid_for(rows, LNP_WAVES, 8192);
+    bf16_t* y = static_cast<bf16_t*>(y_bf16);
+    if (x_dtype == NRV_F32) hipLaunchKernelGGL((ln_pad_fwd_kernel<true>), dim3(grid), dim3(LNP_THREADS), 0, s, x, gamma, beta, y, mean, rstd, (long long)rows, n, (int)ld, eps);
+    else hipLaunchKernelGGL((ln_pad_fwd_kernel<false>), dim3(grid), dim3(LNP_THREADS), 0, s, x, gamma, beta, y, mean, rstd, (long long)rows, n, (int)ld, eps);
+    NRV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" size_t nrv_layernorm_pad_bwd_workspace(int64_t rows, int n) {
+    if (rows <= 0 || n <= 0) return 0;
+    return (size_t)lnp_slabs(rows) * 2 * (size_t)n * sizeof(float);
+}
+
+extern "C" int nrv_layernorm_pad_bwd(const void* dy_bf16, const void* x, int x_dtype, const float* gamma, const float* mean,
+                                     const float* rstd, const void* dres, int dres_dtype, float* dx_f32, void* dx_bf16,
+                                     float* dgamma, float* dbeta, int accumulate, void* workspace, size_t workspace_bytes,
+                                     int64_t rows, int n, int64_t ld, void* stream) {
+    if (lnp_shape(rows, n, ld)) return NRV_ERR_SHAPE;
+    if (!dy_bf16 || !x || !gamma || !mean || !rstd || !dgamma || !dbeta || !workspace || (!dx_f32 && !dx_bf16)) return NRV_ERR_NULL;
+    if ((x_dtype != NRV_F32 && x_dtype != NRV_BF16) || (dres && dres_dtype != NRV_F32 && dres_dtype != NRV_BF16)) return NRV_ERR_DTYPE;
+    if (workspace_bytes < nrv_layernorm_pad_bwd_workspace(rows, n)) return NRV_ERR_WORKSPACE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bf16_t* dy = static_cast<const bf16_t*>(dy_bf16);
+    bf16_t* dx16 = static_cast<bf16_t*>(dx_bf16);
+    const int grid = grid_for(rows, LNP_WAVES, 8192);
+    const bool xf = x_dtype == NRV_F32, rf = !dres || dres_dtype == NRV_F32;
+    if (xf && rf) hipLaunchKernelGGL((ln_pad_bwd_kernel<true, true>), dim3(grid), dim3(LNP_THREADS), 0, s, dy, x, gamma, mean, rstd, dres, dx_f32, dx16, (long long)rows, n, (int)ld);
+    else if (xf) hipLaunchKernelGGL((ln_pad_bwd_kernel<true, false>), dim3(grid), dim3(LNP_THREADS), 0, s, dy, x, gamma, mean, rstd, dres, dx_f32, dx16, (long long)rows, n, (int)ld);
+    else if (rf) hipLaunchKernelGGL((ln_pad_bwd_kernel<false, true>), dim3(grid), dim3(LNP_THREADS), 0, s, dy, x, gamma, mean, rstd, dres, dx_f32, dx16, (long long)rows, n, (int)ld);
+    else hipLaunchKernelGGL((ln_pad_bwd_kernel<false, false>), dim3(grid), dim3(LNP_THREADS), 0, s, dy, x, gamma, mean, rstd, dres, dx_f32, dx16, (long long)rows, n, (int)ld);
+    NRV_CHECK_LAUNCH();
+    const int slabs = lnp_slabs(rows);
+    const long long per = (rows + slabs - 1) / slabs;
+    float* part = static_cast<float*>(workspace);
+    const dim3 pg((unsigned)((n + LNP_THREADS - 1) / LNP_THREADS), (unsigned)slabs);
+    if (xf) hipLaunchKernelGGL((ln_pad_dgb_partial_kernel<true>), pg, dim3(LNP_THREADS), 0, s, dy, x, mean, rstd, part, (long long)rows, per, n, (int)ld);
+    else hipLaunchKernelGGL((ln_pad_dgb_partial_kernel<false>), pg, dim3(LNP_THREADS), 0, s, dy, x, mean, rstd, part, (long long)rows, per, n, (int)ld);
+    NRV_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ln_pad_dgb_final_kernel, dim3(pg.x), dim3(LNP_THREADS), 0, s, part, dgamma, dbeta, slabs, n, accumulate);
+    NRV_CHECK_LAUNCH();
+    return 0;
+}

@@ -1423,3 +1423,129 @@ def head_mix_bwd(dout: Tensor, x: Tensor, W: Tensor):
          lambda: lib.nrv_head_mix_bwd(dout.data_ptr(), x.data_ptr(), W.data_ptr(), din.data_ptr(), dW.data_ptr(), ws.data_ptr(),
                                       ws.numel(), B, H, Nq, Nk, _stream()), "nrv_head_mix_bwd")
     return din, dW
+
+
+# ----------------------------------------------------------------------------------------------
+# tokens-to-token (t2t.py): soft split, LayerNorm over n of ld columns, wide-head streaming attention
+# ----------------------------------------------------------------------------------------------
+ATTN_WIDE_MAX_DH = 192           # include/nrv.h nrv_attn_wide_*: 128 < dh <= 192, dh % 8 == 0
+
+
+def pad8(n: int) -> int:
+    return (n + 7) // 8 * 8
+
+
+def soft_split_fwd(src: Tensor, B: int, C: int, H: int, W: int, ks: int, stride: int, pad: int, rows: bool) -> Tensor:
+    """nn.Unfold(ks, stride, pad) -> cols bf16 [B*Ho*Wo, pad8(ks*ks*C)], feature (c, ky, kx).  `rows`: src is bf16 token rows
+    [B*H*W, ld >= C]; otherwise the NCHW image, fp32 | bf16."""
+    _dev(src, "src")
+    if rows:
+        _bf16(src, "src")
+        T, _, ld = _rows2d(src, "src")
+        if T != B * H * W or src.shape[1] < C:
+            raise NrvError(f"soft_split_fwd: src is {tuple(src.shape)}, expected [{B * H * W}, >= {C}]")
+    else:
+        ld = 0
+        if not src.is_contiguous() or tuple(src.shape) != (B, C, H, W):
+            raise NrvError(f"soft_split_fwd: src must be a contiguous [{B}, {C}, {H}, {W}] image")
+    Ho, Wo = conv_out_size(H, ks, stride, pad), conv_out_size(W, ks, stride, pad)
+    if Ho <= 0 or Wo <= 0:
+        raise NrvError("soft_split_fwd: empty output grid")
+    cols = torch.empty(B * Ho * Wo, pad8(ks * ks * C), dtype=torch.bfloat16, device=src.device)
+    lib = _lib.load()
+    _run("soft_split_fwd", 0.0, 4 * cols.numel(),
+         lambda: lib.nrv_soft_split_fwd(src.data_ptr(), _dt(src, "src"), _lib.SPLIT_ROWS if rows else _lib.SPLIT_NCHW, ld, cols.data_ptr(),
+                                        B, C, H, W, ks, stride, pad, _stream()),
+         "nrv_soft_split_fwd")
+    return cols
+
+
+def soft_split_bwd(dcols: Tensor, B: int, C: int, H: int, W: int, ks: int, stride: int, pad: int, ld: Optional[int] = None) -> Tensor:
+    """dx fp32 token rows [B*H*W, ld] (default pad8(C); columns >= C zero) of soft_split_fwd, from dcols bf16."""
+    _bf16(dcols, "dcols")
+    Ho, Wo = conv_out_size(H, ks, stride, pad), conv_out_size(W, ks, stride, pad)
+    if not dcols.is_contiguous() or tuple(dcols.shape) != (B * Ho * Wo, pad8(ks * ks * C)):
+        raise NrvError(f"soft_split_bwd: dcols is {tuple(dcols.shape)}, expected a contiguous [{B * Ho * Wo}, {pad8(ks * ks * C)}]")
+    ld = pad8(C) if ld is None else ld
+    dx = torch.empty(B * H * W, ld, dtype=torch.float32, device=dcols.device)
+    lib = _lib.load()
+    _run("soft_split_bwd", 0.0, 2 * dcols.numel() + 4 * dx.numel(),
+         lambda: lib.nrv_soft_split_bwd(dcols.data_ptr(), dx.data_ptr(), ld, B, C, H, W, ks, stride, pad, _stream()),
+         "nrv_soft_split_bwd")
+    return dx
+
+
+def layernorm_pad_fwd(x: Tensor, n: int, gamma: Tensor, beta: Tensor, eps: float):
+    """x [rows, ld] fp32|bf16 with n true columns -> (y bf16 [rows, ld] with zero pad columns, mean, rstd)."""
+    _dev(x, "x"); _f32(gamma, "gamma"); _f32(beta, "beta")
+    rows, _, ld = _rows2d(x, "x")
+    if x.shape[1] != ld or gamma.numel() != n or beta.numel() != n:
+        raise NrvError(f"layernorm_pad_fwd: x must be dense [rows, ld] and gamma / beta hold n = {n} elements")
+    y = torch.empty(rows, ld, dtype=torch.bfloat16, device=x.device)
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    _run("layernorm_pad_fwd", 0.0, rows * ld * (x.element_size() + 2),
+         lambda: lib.nrv_layernorm_pad_fwd(x.data_ptr(), _dt(x, "x"), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
+                                           mean.data_ptr(), rstd.data_ptr(), rows, n, ld, float(eps), _stream()),
+         "nrv_layernorm_pad_fwd")
+    return y, mean, rstd
+
+
+def layernorm_pad_bwd(dy: Tensor, x: Tensor, n: int, gamma: Tensor, mean: Tensor, rstd: Tensor, dres: Optional[Tensor] = None,
+                      want_f32: bool = True, want_bf16: bool = False):
+    """(dx_f32|None, dx_bf16|None, dgamma [n], dbeta [n]); dx = dres + LN'(dy) on the n true columns, zero pad columns."""
+    _bf16(dy, "dy"); _dev(x, "x"); _f32(gamma, "gamma"); _f32(mean, "mean"); _f32(rstd, "rstd")
+    rows, _, ld = _rows2d(x, "x")
+    if x.shape[1] != ld or tuple(dy.shape) != (rows, ld) or not dy.is_contiguous() or gamma.numel() != n:
+        raise NrvError("layernorm_pad_bwd: x and dy must be dense [rows, ld], gamma holds n elements")
+    if dres is not None and (tuple(dres.shape) != (rows, ld) or not dres.is_contiguous()):
+        raise NrvError("layernorm_pad_bwd: dres must be dense [rows, ld]")
+    if not (want_f32 or want_bf16):
+        raise NrvError("layernorm_pad_bwd: nothing asked for")
+    lib = _lib.load()
+    dx32 = torch.empty(rows, ld, dtype=torch.float32, device=x.device) if want_f32 else None
+    dx16 = torch.empty(rows, ld, dtype=torch.bfloat16, device=x.device) if want_bf16 else None
+    dgamma = torch.empty(n, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty(n, dtype=torch.float32, device=x.device)
+    ws = _workspace(lib.nrv_layernorm_pad_bwd_workspace(rows, n), x.device)
+    _run("layernorm_pad_bwd", 0.0, rows * ld * (2 * (2 + x.element_size()) + (dres.element_size() if dres is not None else 0) + 4),
+         lambda: lib.nrv_layernorm_pad_bwd(dy.data_ptr(), x.data_ptr(), _dt(x, "x"), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                           _ptr(dres), _dt(dres, "dres") if dres is not None else 0, _ptr(dx32), _ptr(dx16),
+                                           dgamma.data_ptr(), dbeta.data_ptr(), 0, ws.data_ptr(), ws.numel(), rows, n, ld, _stream()),
+         "nrv_layernorm_pad_bwd")
+    return dx32, dx16, dgamma, dbeta
+
+
+def attn_wide_shape(dh: int) -> bool:
+    return dh % 8 == 0 and 128 < dh <= ATTN_WIDE_MAX_DH
+
+
+def attn_wide_fwd(qkv: Tensor, B: int, N: int, H: int, dh: int, scale: float):
+    """qkv bf16 [B*N, 3*H*dh], 128 < dh <= 192 -> (out bf16 [B*N, H*dh], lse fp32 [B,H,N]); streaming softmax, no [N, N] matrix."""
+    _bf16(qkv, "qkv")
+    if not qkv.is_contiguous() or qkv.numel() != B * N * 3 * H * dh:
+        raise NrvError("attn_wide_fwd: qkv must be contiguous [B*N, 3*H*dh]")
+    out = torch.empty(B * N, H * dh, dtype=torch.bfloat16, device=qkv.device)
+    lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
+    lib = _lib.load()
+    _run("attn_wide_fwd", 4.0 * B * H * N * N * dh, 2 * B * N * H * dh * 4,
+         lambda: lib.nrv_attn_wide_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, N, H, dh, float(scale), _stream()),
+         "nrv_attn_wide_fwd")
+    return out, lse
+
+
+def attn_wide_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, B: int, N: int, H: int, dh: int, scale: float) -> Tensor:
+    _bf16(qkv, "qkv"); _bf16(out, "out"); _bf16(dout, "dout"); _f32(lse, "lse")
+    if not (qkv.is_contiguous() and out.is_contiguous() and dout.is_contiguous() and lse.is_contiguous()):
+        raise NrvError("attn_wide_bwd: operands must be contiguous")
+    if qkv.numel() != B * N * 3 * H * dh or out.numel() != B * N * H * dh or dout.numel() != out.numel() or lse.numel() != B * H * N:
+        raise NrvError("attn_wide_bwd: operand sizes do not match B, N, H, dh")
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty(B * H * N, dtype=torch.float32, device=qkv.device)
+    lib = _lib.load()
+    _run("attn_wide_bwd", 10.0 * B * H * N * N * dh, 2 * B * N * H * dh * 8,
+         lambda: lib.nrv_attn_wide_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(),
+                                       delta.data_ptr(), B, N, H, dh, float(scale), _stream()),
+         "nrv_attn_wide_bwd")
+    return dqkv

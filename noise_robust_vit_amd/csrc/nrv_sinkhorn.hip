@@ -27,8 +27,6 @@ namespace {
 
 using namespace nrv_attn;
 
-typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;   // the backward kernel's resident copy of one P0 tile
-
 constexpr int SK_THREADS = 1024;      // 16 waves: one 16-query tile each (N <= 256)
 constexpr int SK_WAVES = 16;
 constexpr int SK_TPW = 2;             // query tiles per wave of the backward kernel
@@ -439,15 +437,19 @@ __global__ __launch_bounds__(1024 / TPW, TPW == 1 ? 4 : 2) void sinkhorn_bwd_ker
             out[e] = pv;
         }
     };
-    // P0 is computed ONCE (in the dV phase) and kept in registers as fp16 (values in [0, 1]: 11 significant bits, everything
-    // below 6e-8 -- exp2 of less than -24 -- reads back as zero); the walk reads it through v_fma_mix_f32 (fp16 operand, fp32
-    // arithmetic).  Recomputing it instead (MFMA + v_exp_f32, which issues at a quarter of the VALU rate) in each of the 9
-    // later passes was 40 % of the kernel's VALU cycles.
-    u32x2_t P0h[TPW][NT];           // f16x4_t bit patterns
-    auto p0h = [&](int u, int kt) {
+    // P0 is computed ONCE (in the dV phase) and kept in registers as bf16: 8 significant bits -- the grade of P7's and dS's own
+    // rounding -- over the FULL fp32 exponent range.  (An fp16 copy read back everything below 2^-24 as zero and had fewer than
+    // 11 bits below 6e-5: the column steps rescale exactly those entries to O(1/N), and the dK / dV rows of a key 12 - 20 nats
+    // below the rest were 30 - 100 % wrong; tests/test_peaked_attn_gpu.py.)  The walk unpacks a pair with one shift and one
+    // mask.  Recomputing P0 instead (MFMA + v_exp_f32, which issues at a quarter of the VALU rate) in each of the 9 later
+    // passes was 40 % of the kernel's VALU cycles.
+    u32x2_t P0b[TPW][NT];           // 4 bf16 bit patterns
+    auto p0b = [&](int u, int kt) {
         // opaque per use: hipcc would otherwise convert every tile back ONCE and keep the fp32 copy live (spilled)
-        asm volatile("" : "+v"(P0h[u][kt]));
-        return __builtin_bit_cast(f16x4_t, P0h[u][kt]);
+        asm volatile("" : "+v"(P0b[u][kt]));
+        const u32x2_t w = P0b[u][kt];
+        return f32x4_t{__uint_as_float(w[0] << 16), __uint_as_float(w[0] & 0xffff0000u),
+                       __uint_as_float(w[1] << 16), __uint_as_float(w[1] & 0xffff0000u)};
     };
 
     // key-owner side: this wave's key tiles are wave + SKQ_WAVES s; the chunk rows are queries u CH .. of slot u
@@ -528,8 +530,8 @@ __global__ __launch_bounds__(1024 / TPW, TPW == 1 ? 4 : 2) void sinkhorn_bwd_ker
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) st = mfma16(kr[kt & 1][ks], qf[u][ks], st);
                 p0_from(st, kt, u, p0u);              // zero for the queries of a tile slot beyond the head (lse2 = inf)
-                P0h[u][kt] = __builtin_bit_cast(u32x2_t, __builtin_convertvector(p0u, f16x4_t));
-                asm volatile("" : "+v"(P0h[u][kt]));                  // convert here, not at the first use (the fp32 tile would stay live)
+                P0b[u][kt] = u32x2_t{pack_bf16x2(p0u[0], p0u[1]), pack_bf16x2(p0u[2], p0u[3])};
+                asm volatile("" : "+v"(P0b[u][kt]));                  // convert here, not at the first use (the fp32 tile would stay live)
             }
         }
     }
@@ -555,11 +557,11 @@ __global__ __launch_bounds__(1024 / TPW, TPW == 1 ? 4 : 2) void sinkhorn_bwd_ker
 #pragma unroll
             for (int kt = 0; kt < NT; ++kt) {
                 SK_KEEP_ORDER();
-                const f16x4_t ph = p0h(u, kt);
+                const f32x4_t ph = p0b(u, kt);
                 const f32x4_t b3 = *reinterpret_cast<const f32x4_t*>(bv + 3 * NP + kt * 16 + 4 * g);
                 const float a4 = av[u][4];                                    // 0 for inactive tiles / padded queries
                 const f32x4_t ab = b3 * f32x4_t{a4, a4, a4, a4};
-                const u32x2_t pk = {pack_bf16x2((float)ph[0] * ab[0], (float)ph[1] * ab[1]), pack_bf16x2((float)ph[2] * ab[2], (float)ph[3] * ab[3])};
+                const u32x2_t pk = {pack_bf16x2(ph[0] * ab[0], ph[1] * ab[1]), pack_bf16x2(ph[2] * ab[2], ph[3] * ab[3])};
                 *reinterpret_cast<u32x2_t*>(chunk + chunk_wr + kt * 32) = pk;
             }
             __syncthreads();
@@ -624,10 +626,10 @@ __global__ __launch_bounds__(1024 / TPW, TPW == 1 ? 4 : 2) void sinkhorn_bwd_ker
                 const f32x4_t b4 = *reinterpret_cast<const f32x4_t*>(bt + kt * 16 + 4 * g);
 #pragma unroll
                 for (int u = 0; u < TPW; ++u) {
-                    const f16x4_t ph = p0h(u, kt);
+                    const f32x4_t ph = p0b(u, kt);
                     const f32x4_t gb = G[u][kt] * b4;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) rho[u] = __builtin_fmaf((float)ph[e], gb[e], rho[u]);
+                    for (int e = 0; e < 4; ++e) rho[u] = __builtin_fmaf(ph[e], gb[e], rho[u]);
                     asm volatile("" : "+v"(rho[u]));
                 }
             }
@@ -651,12 +653,12 @@ __global__ __launch_bounds__(1024 / TPW, TPW == 1 ? 4 : 2) void sinkhorn_bwd_ker
                 f32x4_t x = {0.f, 0.f, 0.f, 0.f};                            // av = 0 for inactive tiles
 #pragma unroll
                 for (int u = 0; u < TPW; ++u) {
-                    const f16x4_t ph = p0h(u, kt);
+                    const f32x4_t ph = p0b(u, kt);
                     const float au = av[u][t];
                     const f32x4_t a4 = {au, au, au, au};
                     const f32x4_t ga = G[u][kt] * a4;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) x[e] = __builtin_fmaf((float)ph[e], ga[e], x[e]);
+                    for (int e = 0; e < 4; ++e) x[e] = __builtin_fmaf(ph[e], ga[e], x[e]);
                 }
                 return x;
             };
@@ -705,9 +707,9 @@ __global__ __launch_bounds__(1024 / TPW, TPW == 1 ? 4 : 2) void sinkhorn_bwd_ker
         for (int kt = 0; kt < NT; ++kt)
 #pragma unroll
             for (int u = 0; u < TPW; ++u) {
-                const f16x4_t ph = p0h(u, kt);
+                const f32x4_t ph = p0b(u, kt);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) sd[u] = __builtin_fmaf((float)ph[e], G[u][kt][e], sd[u]);
+                for (int e = 0; e < 4; ++e) sd[u] = __builtin_fmaf(ph[e], G[u][kt][e], sd[u]);
             }
 #pragma unroll
         for (int u = 0; u < TPW; ++u) {
@@ -717,10 +719,10 @@ __global__ __launch_bounds__(1024 / TPW, TPW == 1 ? 4 : 2) void sinkhorn_bwd_ker
             const f32x4_t s4 = {p.scale, p.scale, p.scale, p.scale}, n4 = {ns, ns, ns, ns};
 #pragma unroll
             for (int kt = 0; kt < NT; ++kt) {
-                const f16x4_t ph = p0h(u, kt);
+                const f32x4_t ph = p0b(u, kt);
                 const f32x4_t d = G[u][kt] * s4 + n4;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) G[u][kt][e] = (float)ph[e] * d[e];
+                for (int e = 0; e < 4; ++e) G[u][kt][e] = ph[e] * d[e];
             }
         }
     }

@@ -50,6 +50,18 @@ __device__ __forceinline__ void reduce_columns(float* part /* [SN_WAVES][SN_CHUN
 }
 static_assert(SN_THREADS == SN_CHUNK, "one column per thread in the cross-wave pass");
 
+// exp(d) for P0 = exp(S - lse) with the product d log2(e) carried in two floats.  __expf rounds that product once: at |d| ~ 64 (a
+// column 60 nats below the rest, which the column steps rescale to ordinary weights) that alone is 2^-18 relative, and the fp32
+// constant adds |d| 1.3e-8 with one sign for the whole column -- b_j of such a column was 3e-6 off where torch's fp32 is 2e-7
+// (tests/test_peaked_attn_gpu.py).  -inf / NaN and everything that underflows anyway go through __expf unchanged.
+__device__ __forceinline__ float exp_p0(float d) {
+    const float L = 1.44269502e+0f, L_LO = 1.92596299e-8f;               // log2(e) = L + L_LO
+    const float t = d * L;
+    const float e = fmaf(d, L_LO, fmaf(d, L, -t));
+    const float r = __builtin_amdgcn_exp2f(t) * fmaf(e, 0.693147182f, 1.0f);
+    return d > -100.f ? r : __expf(d);
+}
+
 // forward: scores [G,R,C] -> out [G,R,C]; lse [G,R]; avec [G, iters + 1, R] (cumulative row scalings a_1 .. a_{iters+1});
 // bvec [G, iters, C] (cumulative column scalings b_1 .. b_iters).  LDS: b [64 MAXJ] | lse of the rows [R] | part.
 template <int MAXJ>
@@ -105,7 +117,7 @@ __global__ __launch_bounds__(SN_THREADS) void sinknorm_fwd_kernel(const float* _
             float r = 0.f;
 #pragma unroll
             for (int k = 0; k < MAXJ; ++k) {
-                x[k] = __expf(x[k] - l);                         // P0; exp(-inf) = 0 beyond the row
+                x[k] = exp_p0(x[k] - l);                         // P0; exp(-inf) = 0 beyond the row
                 r = fmaf(x[k], b[lane + 64 * k], r);
             }
             r = wave_sum(r);
@@ -126,7 +138,7 @@ __global__ __launch_bounds__(SN_THREADS) void sinknorm_fwd_kernel(const float* _
         if (last) break;
         // (the first barrier inside reduce_columns comes before any emit: every wave is done reading b by then)
         reduce_columns<MAXJ>(part, acc, C, tid, [&](int j, float sum) {
-            const float v = 1.0f / sum;
+            const float v = sum > 0.f ? 1.0f / sum : 0.f;        // a column that underflowed completely (-inf scores) stays zero
             b[j] = v;
             bg[(long long)it * C + j] = v;
         });
@@ -163,7 +175,7 @@ __global__ __launch_bounds__(SN_THREADS) void sinknorm_bwd_kernel(const float* _
         for (int j = tid; j < CP; j += SN_THREADS) {
             const float bprev = (it > 0 && j < C) ? bg[(long long)(it - 1) * C + j] : 1.0f;
             bp[j] = bprev;
-            cinv[j] = (it < iters && j < C) ? bg[(long long)it * C + j] / bprev : 1.0f;
+            cinv[j] = (it < iters && j < C) ? (bprev > 0.f ? bg[(long long)it * C + j] / bprev : 0.f) : 1.0f;
         }
         __syncthreads();
         float acc[MAXJ];
@@ -187,7 +199,7 @@ __global__ __launch_bounds__(SN_THREADS) void sinknorm_bwd_kernel(const float* _
 #pragma unroll
             for (int k = 0; k < MAXJ; ++k) {
                 const int j = lane + 64 * k;
-                x[k] = __expf(x[k] - l) * bp[j];                 // P0 b_prev (zero beyond the row)
+                x[k] = exp_p0(x[k] - l) * bp[j];                 // P0 b_prev (zero beyond the row)
                 G[k] = (G[k] - t[j]) * cinv[j];                  // column step `it` (t = 0, cinv = 1 in the first sweep)
                 s = fmaf(G[k], x[k], s);
             }

@@ -441,6 +441,53 @@ def test_vision_transformer_robust_vit_b_geometry_against_oracle(dev):
     assert abs(loss.item() - ref_loss.item()) < LOSS_TOL_FP32REF
 
 
+def test_vision_transformer_robust_weak_keys_in_every_head_against_oracle(dev):
+    """robust=True with two tokens that are WEAK KEYS in every head (tests/peaked_ref.py weak_key_vit_case: the key third of
+    in_proj_weight and the image are built so that every query of every head scores tokens 5 and 77 at least 12 nats below the
+    rest before the normalisation; asserted here on the CPU).  The Sinkhorn column steps give those keys ordinary weights, so their
+    rows of dK / dV feed every parameter gradient in front of the attention: logits, loss and EVERY parameter gradient against the
+    CPU oracle at the bounds of the test above, through VisionTransformer / encoder.py (the model's own qkv, the saved dict, autograd).
+    Measured on MI355X: logits 4.0e-3 / 2.1e-3, loss 2.79191 vs 2.79110, worst gradient 8.1e-3 (conv_proj.weight)."""
+    import peaked_ref as PR
+    from noise_robust_vit_amd import VisionTransformer
+    from oracle import vit_oracle as V
+    from oracle.simple_vit_oracle import cross_entropy_ls
+    cfg = dict(image_size=224, patch_size=16, num_layers=1, num_heads=12, hidden_dim=768, mlp_dim=3072, num_classes=13)
+    sd = V.vit_init_state_dict(seed=3, **cfg)
+    g = torch.Generator().manual_seed(5)
+    for k in sd:
+        if k.endswith("bias") or k == "class_token":
+            sd[k] = torch.randn(sd[k].shape, generator=g) * 0.1
+    x = torch.randn(2, 3, 224, 224, generator=g)
+    y = torch.randint(0, 13, (2,), generator=g)
+    sd, x, logw = PR.weak_key_vit_case(sd, x, patch_size=16, num_heads=12)
+    print(f"VT robust weak keys: log-weights of tokens 5 / 77 before the normalisation: max {logw.amax(dim=(0, 1, 2)).tolist()}, "
+          f"min {logw.amin(dim=(0, 1, 2)).tolist()}")
+    assert logw.max().item() < -12.0
+    model = VisionTransformer(**cfg, robust=True)
+    model.load_state_dict(sd)
+    model = model.to(dev).train()
+    logits = model(x.to(dev))
+    loss = torch.nn.functional.cross_entropy(logits, y.to(dev), label_smoothing=0.1)
+    loss.backward()
+    torch.set_num_threads(8)
+    leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    ref = V.vit_forward(leaves, x, patch_size=16, num_heads=12, robust=True)
+    ref_loss = cross_entropy_ls(ref, y)
+    ref_loss.backward()
+    emu = V.vit_forward(sd, x, patch_size=16, num_heads=12, robust=True, emulate_bf16=True)
+    e_ref, e_emu = relmax(logits, ref), relmax(logits, emu)
+    rows = []
+    for name, p in model.named_parameters():
+        gk, r = p.grad.detach().float().cpu().reshape(-1), leaves[name].grad.float().reshape(-1)
+        rows.append((((gk - r).norm() / r.norm().clamp_min(1e-30)).item(), name))
+    print(f"VT robust weak keys: logits vs fp32 oracle {e_ref:.3e}, vs emulating oracle {e_emu:.3e}, loss {loss.item():.6f} vs "
+          f"{ref_loss.item():.6f}; grad rel-L2 worst three {sorted(rows, reverse=True)[:3]}")
+    check_grads(model, {k: v.grad for k, v in leaves.items()}, tol=ROBUST_VT_BOUNDS[2])
+    assert e_ref < ROBUST_VT_BOUNDS[0] and e_emu < ROBUST_VT_BOUNDS[1]
+    assert abs(loss.item() - ref_loss.item()) < LOSS_TOL_FP32REF
+
+
 @pytest.mark.parametrize("case", ["vit_h_14_l1", "vit_b_16_384px_l1"])
 def test_vision_transformer_robust_beyond_the_fused_shapes_against_oracle(dev, case):
     """robust=True where the head's [N, N] matrix does not stay on chip -- vit_h_14 (257 tokens, 16 heads x 80; vit.py:512-519)

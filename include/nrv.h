@@ -298,7 +298,9 @@ int nrv_bn_bwd(const void* dz, int dz_dtype, int act, const float* keep, float s
  *                    columns >= ks*ks*C.  The GEMM weight image is the Conv2d weight permuted to [Cout, ks, ks, C].
  *   nrv_conv_fold  : the input gradient, dx fp32 NHWC rows [B*H*W, C] from dcols bf16 [B*Ho*Wo, KP], in gather form: each
  *                    input element sums its (ky, kx) contributions in ky-then-kx order (no scatter, no atomics).
- *   Ho = (H + 2 pad - ks) / stride + 1; ks <= 7, pad < ks.  cols 16-byte aligned (and src for NHWC). */
+ *   Ho = (H + 2 pad - ks) / stride + 1; ks <= 7, pad < ks.  cols 16-byte aligned (and src for NHWC).
+ *   nrv_conv_unfold / nrv_conv_fold and nrv_soft_split_fwd / nrv_soft_split_bwd (below) are one unfold / fold kernel pair
+ *   (csrc/nrv_misc.hip) with two feature orders: tap-major (ky, kx, c) here, channel-major (c, ky, kx) there. */
 #define NRV_CONV_NCHW 0
 #define NRV_CONV_NHWC 1
 int nrv_conv_unfold(const void* src, int src_dtype, int src_layout, void* cols_bf16,
@@ -532,7 +534,8 @@ int nrv_adamw_f32(float* p, const void* grad, int grad_dtype, float* m, float* v
  *                    ignored) or bf16 token rows [B*H*W, ld_src] (NRV_SPLIT_ROWS, ld_src >= C: RearrangeImage is the
  *                    addressing) -> cols bf16 [B*Ho*Wo, KP], feature c*ks*ks + ky*ks + kx (nn.Unfold's order; nrv_conv_unfold
  *                    writes (ky, kx, c)), KP = ks*ks*C rounded up to 8.  Taps outside the image and columns >= ks*ks*C are
- *                    zeros.  A copy: bf16 sources arrive bit-exact, fp32 ones rounded to nearest even.
+ *                    zeros.  A copy: bf16 sources arrive bit-exact, fp32 ones rounded to nearest even.  The channel-major
+ *                    instantiation of the unfold / fold kernel pair behind nrv_conv_unfold / nrv_conv_fold.
  *   nrv_soft_split_bwd: its input gradient, a fold in gather form: dx fp32 rows [B*H*W, ld_dx] (ld_dx >= C; columns >= C
  *                    are written as zeros) from dcols bf16 [B*Ho*Wo, KP].  Each element sums the at most ceil(ks / stride)^2
  *                    windows that cover it, ky then kx ascending: no scatter, no atomics, reruns are bit-identical.

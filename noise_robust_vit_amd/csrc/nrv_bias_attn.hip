@@ -15,10 +15,11 @@
 //             in-thread, column steps through a column sum); P0 is recomputed from the scores and lse where a step needs it.
 //             dS = P0 (G - rowsum(G P0)); dQ in the row threads, dK = scale dS^T Q and dV = P^T dO in the column threads.
 //             The table gradient folds dS through the inverse index (a CSR list of the (i, j) of every table entry, built by the
-//             host once per geometry) into one partial per (head, entry, sample); a second kernel sums the partials of an entry
-//             over the samples in a fixed order.  No atomics: reruns are bit-identical.
-// Nothing [B, H, Nq, Nk]-sized reaches HBM.
-#include "nrv_common.hpp"
+//             host once per geometry) into one partial per (head, entry, sample); reduce_partials_kernel (nrv_rows.hpp) sums the
+//             partials of an entry over the samples in a fixed order.  No atomics: reruns are bit-identical.
+// Nothing [B, H, Nq, Nk]-sized reaches HBM.  The row helpers (load_row / dot_row / axpy_row / store_row) and Hardswish are those of
+// nrv_rows.hpp.
+#include "nrv_rows.hpp"
 
 #include <cmath>
 
@@ -54,69 +55,14 @@ struct BiasParams {
     float scale;
 };
 
-__device__ __forceinline__ float hswish(float x) { return x * fminf(fmaxf(x + 3.f, 0.f), 6.f) / 6.f; }
-__device__ __forceinline__ float hswish_grad(float x) { return x < -3.f ? 0.f : (x <= 3.f ? x / 3.f + 0.5f : 1.f); }
-
-template <int N>
-__device__ __forceinline__ void load_row(const bf16_t* src, float (&r)[N]) {
-#pragma unroll
-    for (int c = 0; c < N / 8; ++c) {
-        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(src + c * 8);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            r[c * 8 + 2 * e] = bf16lo_to_f32(v[e]);
-            r[c * 8 + 2 * e + 1] = bf16hi_to_f32(v[e]);
-        }
-    }
-}
-
-template <int N>
-__device__ __forceinline__ float dot_row(const float (&a)[N], const bf16_t* row) {
-    float acc = 0.f;
-#pragma unroll
-    for (int c = 0; c < N / 8; ++c) {
-        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(row + c * 8);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            acc = fmaf(a[c * 8 + 2 * e], bf16lo_to_f32(v[e]), acc);
-            acc = fmaf(a[c * 8 + 2 * e + 1], bf16hi_to_f32(v[e]), acc);
-        }
-    }
-    return acc;
-}
-
-template <int N>
-__device__ __forceinline__ void axpy_row(float w, const bf16_t* row, float (&acc)[N]) {
-#pragma unroll
-    for (int c = 0; c < N / 8; ++c) {
-        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(row + c * 8);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            acc[c * 8 + 2 * e] = fmaf(w, bf16lo_to_f32(v[e]), acc[c * 8 + 2 * e]);
-            acc[c * 8 + 2 * e + 1] = fmaf(w, bf16hi_to_f32(v[e]), acc[c * 8 + 2 * e + 1]);
-        }
-    }
-}
-
-template <int N>
-__device__ __forceinline__ void store_row(bf16_t* dst, const float (&r)[N], float mul) {
-#pragma unroll
-    for (int c = 0; c < N / 8; ++c) {
-        u32x4_t v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = pack_bf16x2(r[c * 8 + 2 * e] * mul, r[c * 8 + 2 * e + 1] * mul);
-        *reinterpret_cast<u32x4_t*>(dst + c * 8) = v;
-    }
-}
-
 // 8 consecutive elements of a dO row = dA * Hardswish'(O) (the proj branch's activation, levit.py:229-232)
 __device__ __forceinline__ void load_do8(const bf16_t* da, const bf16_t* o, float (&r)[8]) {
     const u32x4_t a = *reinterpret_cast<const u32x4_t*>(da);
     const u32x4_t ov = *reinterpret_cast<const u32x4_t*>(o);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        r[2 * e] = bf16lo_to_f32(a[e]) * hswish_grad(bf16lo_to_f32(ov[e]));
-        r[2 * e + 1] = bf16hi_to_f32(a[e]) * hswish_grad(bf16hi_to_f32(ov[e]));
+        r[2 * e] = bf16lo_to_f32(a[e]) * hardswish_grad(bf16lo_to_f32(ov[e]));
+        r[2 * e + 1] = bf16hi_to_f32(a[e]) * hardswish_grad(bf16hi_to_f32(ov[e]));
     }
 }
 
@@ -242,7 +188,7 @@ __global__ __launch_bounds__(BA_THREADS) void battn_fwd_kernel(BiasParams p) {
         store_row<DV>(p.o + orow, o, 1.f);
         float ho[DV];
 #pragma unroll
-        for (int d = 0; d < DV; ++d) ho[d] = hswish(o[d]);
+        for (int d = 0; d < DV; ++d) ho[d] = hardswish(o[d]);
         store_row<DV>(p.ao + orow, ho, 1.f);
     }
 }
@@ -376,22 +322,6 @@ __global__ __launch_bounds__(BA_THREADS) void battn_bwd_kernel(BiasParams p) {
     }
 }
 
-// dtable[h, t] = sum over samples of part[h, t, b]: thread k adds samples k, k + 256, ... in order, then a fixed tree
-__global__ __launch_bounds__(256) void battn_table_reduce_kernel(const float* __restrict__ part, float* __restrict__ dtable, int B) {
-    __shared__ float red[256];
-    const long long e = blockIdx.x;          // h * T + t
-    const float* src = part + e * B;
-    float acc = 0.f;
-    for (int c = threadIdx.x; c < B; c += 256) acc += src[c];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) dtable[e] = red[0];
-}
-
 size_t lds_bytes(int Nq, int Nk, bool bwd) {
     return ((size_t)Nq * (Nk + 1) + (bwd ? BA_BWD_EXTRA : BA_FWD_EXTRA)) * sizeof(float);
 }
@@ -440,7 +370,8 @@ int launch_bwd(const BiasParams& p, float* dtable, hipStream_t s) {
     if (attr) return attr;
     hipLaunchKernelGGL((battn_bwd_kernel<KD, DV, R>), dim3((unsigned)(p.B * p.H)), dim3(BA_THREADS), lds, s, p);
     NRV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(battn_table_reduce_kernel, dim3((unsigned)(p.H * p.T)), dim3(256), 0, s, p.part, dtable, p.B);
+    // dtable[h, t] = sum over the samples of part[h, t, b]
+    hipLaunchKernelGGL((reduce_partials_kernel<256>), dim3((unsigned)(p.H * p.T)), dim3(256), 0, s, p.part, dtable, p.B, 1ll, 0ll);
     NRV_CHECK_LAUNCH();
     return 0;
 }

@@ -11,8 +11,8 @@
 //   backward  : dz = upstream (x Hardswish'(z) where the activation sits, x the drop-path factor); per (chunk, column) partials of
 //               sum dz and sum dz x^ merged per column like the statistics; dgamma = sum dz x^, dbeta = sum dz;
 //               dy = gamma invstd (dz - mean(dz) - x^ mean(dz x^)) (training) or gamma invstd dz (eval), stored as bf16.
-// No atomics: every sum has one fixed order, reruns are bit-identical.
-#include "nrv_common.hpp"
+// No atomics: every sum has one fixed order, reruns are bit-identical.  Hardswish and its derivative are those of nrv_rows.hpp.
+#include "nrv_rows.hpp"
 
 #include <cmath>
 
@@ -21,10 +21,6 @@ namespace {
 constexpr int BN_CHUNK = 512;     // rows per partial (fixed: the summation order depends on T and C only)
 constexpr int BN_COLS = 64;       // columns per workgroup
 constexpr int BN_GROUPS = 4;      // row groups per workgroup (256 threads)
-
-__device__ __forceinline__ float hardswish(float x) { return x * fminf(fmaxf(x + 3.f, 0.f), 6.f) / 6.f; }
-// torch's hardswish_backward boundaries: 0 below -3, x / 3 + 1/2 on [-3, 3], 1 above
-__device__ __forceinline__ float hardswish_grad(float x) { return x < -3.f ? 0.f : (x <= 3.f ? x / 3.f + 0.5f : 1.f); }
 
 __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __restrict__ y, float* __restrict__ part,
                                                                long long T, int C) {
@@ -236,11 +232,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwd a) {
     }
 }
 
-int grid_for(long long items, int block) {
-    long long g = (items + block - 1) / block;
-    return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
-}
-
 int bn_shape(long long T, int C) {
     if (T <= 0 || C <= 0 || (C & 3) || T > (1ll << 24) || T * C > (1ll << 40)) return NRV_ERR_SHAPE;
     return 0;
@@ -289,7 +280,7 @@ extern "C" int nrv_bn_apply(const float* y, const float* mean, const float* scal
         return NRV_ERR_ALIGN;
     BnApply a{y, mean, scale, gamma, beta, residual, keep, out_f32, static_cast<bf16_t*>(out_bf16), eps, survival, T,
               keep ? rows_per_sample : 1, C, scale_is_var ? 1 : 0, act};
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(T * C / 4, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(T * C / 4, 256, 8192)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     NRV_CHECK_LAUNCH();
     return 0;
 }
@@ -316,7 +307,7 @@ extern "C" int nrv_bn_bwd(const void* dz, int dz_dtype, int act, const float* ke
     NRV_CHECK_LAUNCH();
     hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((unsigned)nrv_cdiv(C, 4)), dim3(256), 0, s, a);
     NRV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(T * C, 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(T * C, 256, 8192)), dim3(256), 0, s, a);
     NRV_CHECK_LAUNCH();
     return 0;
 }

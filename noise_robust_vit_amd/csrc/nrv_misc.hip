@@ -1,6 +1,7 @@
 // Data-movement kernels around the encoder hot path (gfx950): patch unfold, weight staging
-// (fp32 -> bf16 + transposed bf16), casts, token gather/scatter, and the hardware-assumption probes.
-#include "nrv_common.hpp"
+// (fp32 -> bf16 + transposed bf16), casts, token gather/scatter, the hardware-assumption probes, and the one unfold (im2col) /
+// fold kernel pair behind the convolution stems (LeViT, PatchConvNet) and the soft split of T2T-ViT.
+#include "nrv_rows.hpp"
 
 namespace {
 
@@ -247,27 +248,42 @@ __global__ __launch_bounds__(64) void probe_kernel(int which, const bf16_t* __re
 }
 
 // ---------------------------------------------------------------------------------------------
-// convolution as unfold + GEMM (LeViT's b16 stem, levit.py:166-175: Conv2d(3x3, stride 2, pad 1) without bias)
-//   unfold: src (NCHW image, fp32|bf16, or NHWC rows bf16 [B*H*W, C]) -> cols bf16 [B*Ho*Wo, KP], feature (ky, kx, c),
-//           KP = ks*ks*C rounded up to 8; padding and columns >= ks*ks*C read as zero
-//   fold  : the input gradient in gather form: dx[b, y, x, c] = sum over the (ky, kx) with (y + pad - ky) / stride = oy in
-//           range (and exact) of dcols[(b, oy, ox), (ky, kx, c)], ky then kx ascending (a fixed order; no scatter)
-// one thread = 8 consecutive output features of unfold, one input element of fold
+// unfold (im2col) and its fold, one kernel pair with two feature orders:
+//   tap-major     (ky, kx, c): convolution as unfold + GEMM (LeViT's b16 stem, levit.py:166-175: Conv2d(3x3, stride 2, pad 1)
+//                              without bias; the PatchConvNet stem), nrv_conv_unfold / nrv_conv_fold
+//   channel-major (c, ky, kx): nn.Unfold's order, the soft split of T2T-ViT (t2t.py:58-93), nrv_soft_split_fwd / _bwd
+//   unfold: src (NCHW image, fp32 | bf16, or bf16 token rows [B*H*W, ld]: NHWC, the 'b (h w) c -> b c h w' of RearrangeImage is
+//           the addressing) -> cols bf16 [B*Ho*Wo, KP], KP = ks*ks*C rounded up to 8; taps outside the image and columns
+//           >= ks*ks*C are zero.  fp32 sources are rounded once (nearest even), bf16 sources are copied.  One thread = 8
+//           consecutive output features, one 16-byte store.
+//   fold  : the input gradient in gather form: dx[(b, y, x), c] = sum over the windows (oy, ox) that cover (y, x) of
+//           dcols[(b, oy, ox), feature(ky, kx, c)], ky then kx ascending: at most ceil(ks / stride)^2 terms in a fixed order,
+//           fp32, no scatter, no atomics.  dx rows have stride ld; columns C .. ld - 1 are written as zeros.  One thread = one
+//           element of dx.
+// patch_unfold_kernel above is the same operation with ks = stride = p and pad = 0; it stays on its own because it is on the
+// path bench.py times and has its own layout switch and 16-byte path.
 // ---------------------------------------------------------------------------------------------
-struct ConvGeom {
+struct UnfoldGeom {
     int B, C, H, W, Ho, Wo, ks, stride, pad, KP;
+    long long ld;            // row stride of a token-row source (unfold) / of dx (fold)
 };
 
-template <int SRC>      // 0: NCHW fp32, 1: NCHW bf16, 2: NHWC bf16 rows
-__device__ __forceinline__ float conv_src(const void* src, const ConvGeom& g, int b, int c, int iy, int ix) {
-    if (SRC == 0) return reinterpret_cast<const float*>(src)[(((long long)b * g.C + c) * g.H + iy) * g.W + ix];
-    if (SRC == 1) return bf16_to_f32(reinterpret_cast<const bf16_t*>(src)[(((long long)b * g.C + c) * g.H + iy) * g.W + ix]);
-    return bf16_to_f32(reinterpret_cast<const bf16_t*>(src)[(((long long)b * g.H + iy) * g.W + ix) * g.C + c]);
-}
+constexpr int UF_TAP_MAJOR = 0, UF_CHANNEL_MAJOR = 1;      // feature order
+constexpr int UF_NCHW_F32 = 0, UF_NCHW_BF16 = 1, UF_ROWS = 2;   // unfold source
 
+// one source element: fp32 as it is (rounded in pairs on the store), bf16 as its bits (copied)
 template <int SRC>
-__global__ __launch_bounds__(256) void conv_unfold_kernel(const void* __restrict__ src, bf16_t* __restrict__ out, ConvGeom g) {
-    const int F = g.ks * g.ks * g.C, F8 = g.KP >> 3;
+__device__ __forceinline__ auto unfold_src(const void* src, const UnfoldGeom& g, int b, int c, int iy, int ix) {
+    if constexpr (SRC == UF_NCHW_F32) return reinterpret_cast<const float*>(src)[(((long long)b * g.C + c) * g.H + iy) * g.W + ix];
+    else if constexpr (SRC == UF_NCHW_BF16) return (unsigned)reinterpret_cast<const bf16_t*>(src)[(((long long)b * g.C + c) * g.H + iy) * g.W + ix];
+    else return (unsigned)reinterpret_cast<const bf16_t*>(src)[(((long long)b * g.H + iy) * g.W + ix) * g.ld + c];
+}
+__device__ __forceinline__ unsigned bf16_pair(float lo, float hi) { return pack_bf16x2(lo, hi); }
+__device__ __forceinline__ unsigned bf16_pair(unsigned lo, unsigned hi) { return lo | (hi << 16); }
+
+template <int SRC, int ORDER>
+__global__ __launch_bounds__(256) void unfold_kernel(const void* __restrict__ src, bf16_t* __restrict__ out, UnfoldGeom g) {
+    const int kk = g.ks * g.ks, F = kk * g.C, F8 = g.KP >> 3;
     const long long total = (long long)g.B * g.Ho * g.Wo * F8;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const long long t = i / F8;
@@ -275,61 +291,93 @@ __global__ __launch_bounds__(256) void conv_unfold_kernel(const void* __restrict
         const int b = (int)(t / ((long long)g.Ho * g.Wo));
         const int rem = (int)(t - (long long)b * g.Ho * g.Wo);
         const int oy = rem / g.Wo, ox = rem - (rem / g.Wo) * g.Wo;
-        if (SRC == 2 && (g.C & 7) == 0) {
-            // 8 channels of one tap: one 16-byte load of the NHWC row
+        if (SRC == UF_ROWS && ORDER == UF_TAP_MAJOR && (g.C & 7) == 0 && (g.ld & 7) == 0) {
+            // 8 channels of one tap: one 16-byte load of the token row
             const int k = f0 / g.C, c = f0 - k * g.C;
             const int iy = oy * g.stride - g.pad + k / g.ks, ix = ox * g.stride - g.pad + k % g.ks;
             u32x4_t v = {0u, 0u, 0u, 0u};
             if (f0 < F && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W)
-                v = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const bf16_t*>(src) + (((long long)b * g.H + iy) * g.W + ix) * g.C + c);
+                v = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const bf16_t*>(src) + (((long long)b * g.H + iy) * g.W + ix) * g.ld + c);
             *reinterpret_cast<u32x4_t*>(out + t * g.KP + f0) = v;
             continue;
         }
-        float v[8];
+        decltype(unfold_src<SRC>(src, g, 0, 0, 0, 0)) v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int f = f0 + j;
-            const int k = f / g.C, c = f - k * g.C;
-            const int iy = oy * g.stride - g.pad + k / g.ks, ix = ox * g.stride - g.pad + k % g.ks;
-            v[j] = (f < F && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W) ? conv_src<SRC>(src, g, b, c, iy, ix) : 0.f;
+            const int c = ORDER == UF_TAP_MAJOR ? f % g.C : f / kk;
+            const int k = ORDER == UF_TAP_MAJOR ? f / g.C : f - c * kk;
+            const int ky = k / g.ks, kx = k - ky * g.ks;
+            const int iy = oy * g.stride - g.pad + ky, ix = ox * g.stride - g.pad + kx;
+            v[j] = (f < F && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W) ? unfold_src<SRC>(src, g, b, c, iy, ix) : 0;
         }
-        u32x4_t pk = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+        u32x4_t pk = {bf16_pair(v[0], v[1]), bf16_pair(v[2], v[3]), bf16_pair(v[4], v[5]), bf16_pair(v[6], v[7])};
         *reinterpret_cast<u32x4_t*>(out + t * g.KP + f0) = pk;
     }
 }
 
-__global__ __launch_bounds__(256) void conv_fold_kernel(const bf16_t* __restrict__ dcols, float* __restrict__ dx, ConvGeom g) {
-    const long long total = (long long)g.B * g.H * g.W * g.C;
+// PADDED: dx rows may be wider than C (the soft split).  The convolution's rows are exactly C wide; without the per-element
+// c < C test its fold is 0.2 - 0.5 % faster at the LeViT stem shapes (profiles/r08_shared_unfold_and_row_helpers.txt).
+template <int ORDER, bool PADDED>
+__global__ __launch_bounds__(256) void fold_kernel(const bf16_t* __restrict__ dcols, float* __restrict__ dx, UnfoldGeom g) {
+    const int kk = g.ks * g.ks;
+    const long long total = (long long)g.B * g.H * g.W * g.ld;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const long long pix = i / g.C;
-        const int c = (int)(i - pix * g.C);
-        const int b = (int)(pix / ((long long)g.H * g.W));
-        const int rem = (int)(pix - (long long)b * g.H * g.W);
-        const int y = rem / g.W, x = rem - (rem / g.W) * g.W;
+        const long long pix = i / g.ld;
+        const int c = (int)(i - pix * g.ld);
         float acc = 0.f;
-        for (int ky = 0; ky < g.ks; ++ky) {
-            const int ny = y + g.pad - ky;
-            if (ny < 0 || ny % g.stride) continue;
-            const int oy = ny / g.stride;
-            if (oy >= g.Ho) continue;
-            for (int kx = 0; kx < g.ks; ++kx) {
-                const int nx = x + g.pad - kx;
-                if (nx < 0 || nx % g.stride) continue;
-                const int ox = nx / g.stride;
-                if (ox >= g.Wo) continue;
-                acc += bf16_to_f32(dcols[(((long long)b * g.Ho + oy) * g.Wo + ox) * g.KP + (ky * g.ks + kx) * g.C + c]);
+        if (!PADDED || c < g.C) {
+            const int b = (int)(pix / ((long long)g.H * g.W));
+            const int rem = (int)(pix - (long long)b * g.H * g.W);
+            const int y = rem / g.W, x = rem - (rem / g.W) * g.W;
+            for (int ky = 0; ky < g.ks; ++ky) {
+                const int ny = y + g.pad - ky;
+                if (ny < 0 || ny % g.stride) continue;
+                const int oy = ny / g.stride;
+                if (oy >= g.Ho) continue;
+                for (int kx = 0; kx < g.ks; ++kx) {
+                    const int nx = x + g.pad - kx;
+                    if (nx < 0 || nx % g.stride) continue;
+                    const int ox = nx / g.stride;
+                    if (ox >= g.Wo) continue;
+                    const long long row = (((long long)b * g.Ho + oy) * g.Wo + ox) * g.KP;
+                    acc += bf16_to_f32(dcols[ORDER == UF_TAP_MAJOR ? row + (ky * g.ks + kx) * g.C + c : row + c * kk + ky * g.ks + kx]);
+                }
             }
         }
         dx[i] = acc;
     }
 }
 
-int grid_for(long long work_items, int block) {
-    long long g = (work_items + block - 1) / block;
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    return (int)g;
+// the shape rules of the four unfold / fold entry points; fills g
+int unfold_geom(UnfoldGeom& g, int B, int C, int H, int W, int ks, int stride, int pad, long long ld) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ks <= 0 || ks > 7 || stride <= 0 || pad < 0 || pad >= ks) return NRV_ERR_SHAPE;
+    if (H + 2 * pad < ks || W + 2 * pad < ks) return NRV_ERR_SHAPE;
+    g.B = B; g.C = C; g.H = H; g.W = W; g.ks = ks; g.stride = stride; g.pad = pad; g.ld = ld;
+    g.Ho = (H + 2 * pad - ks) / stride + 1;
+    g.Wo = (W + 2 * pad - ks) / stride + 1;
+    g.KP = (ks * ks * C + 7) & ~7;
+    if ((long long)B * g.Ho * g.Wo * g.KP > (1ll << 40) || (long long)B * H * W * (ld > C ? ld : C) > (1ll << 40)) return NRV_ERR_SHAPE;
+    return 0;
 }
+
+// rows: a token-row source; otherwise NCHW of f32 or bf16
+template <int ORDER>
+void launch_unfold(bool rows, bool f32, const void* src, void* cols_bf16, const UnfoldGeom& g, int grid_cap, hipStream_t s) {
+    const int grid = grid_for((long long)g.B * g.Ho * g.Wo * (g.KP >> 3), 256, grid_cap);
+    bf16_t* out = static_cast<bf16_t*>(cols_bf16);
+    if (rows) hipLaunchKernelGGL((unfold_kernel<UF_ROWS, ORDER>), dim3(grid), dim3(256), 0, s, src, out, g);
+    else if (f32) hipLaunchKernelGGL((unfold_kernel<UF_NCHW_F32, ORDER>), dim3(grid), dim3(256), 0, s, src, out, g);
+    else hipLaunchKernelGGL((unfold_kernel<UF_NCHW_BF16, ORDER>), dim3(grid), dim3(256), 0, s, src, out, g);
+}
+
+template <int ORDER, bool PADDED>
+void launch_fold(const void* dcols_bf16, float* dx, const UnfoldGeom& g, int grid_cap, hipStream_t s) {
+    hipLaunchKernelGGL((fold_kernel<ORDER, PADDED>), dim3(grid_for((long long)g.B * g.H * g.W * g.ld, 256, grid_cap)), dim3(256), 0, s,
+                       static_cast<const bf16_t*>(dcols_bf16), dx, g);
+}
+
+constexpr int CONV_GRID_CAP = 4096, SPLIT_GRID_CAP = 16384;     // per call site as chosen with each model; not measured against each other
 
 }  // namespace
 
@@ -357,7 +405,7 @@ extern "C" int nrv_patch_unfold(const void* img, int img_dtype, void* patches_bf
     if (!nrv_aligned16(patches_bf16)) return NRV_ERR_ALIGN;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long long total = (long long)B * (H / p) * (W / p) * ((C * p * p + 7) >> 3);
-    const int grid = grid_for(total, 256);
+    const int grid = grid_for(total, 256, 4096);
     bf16_t* out = static_cast<bf16_t*>(patches_bf16);
     if (img_dtype == NRV_F32) {
         if (layout == NRV_PATCH_P1P2C) hipLaunchKernelGGL((patch_unfold_kernel<true, NRV_PATCH_P1P2C>), dim3(grid), dim3(256), 0, s, img, out, B, C, H, W, p);
@@ -370,42 +418,51 @@ extern "C" int nrv_patch_unfold(const void* img, int img_dtype, void* patches_bf
     return 0;
 }
 
-static int conv_geom(ConvGeom& g, int B, int C, int H, int W, int ks, int stride, int pad) {
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ks <= 0 || ks > 7 || stride <= 0 || pad < 0 || pad >= ks) return NRV_ERR_SHAPE;
-    if (H + 2 * pad < ks || W + 2 * pad < ks) return NRV_ERR_SHAPE;
-    g.B = B; g.C = C; g.H = H; g.W = W; g.ks = ks; g.stride = stride; g.pad = pad;
-    g.Ho = (H + 2 * pad - ks) / stride + 1;
-    g.Wo = (W + 2 * pad - ks) / stride + 1;
-    g.KP = (ks * ks * C + 7) & ~7;
-    if ((long long)B * g.Ho * g.Wo * g.KP > (1ll << 40) || (long long)B * H * W * C > (1ll << 40)) return NRV_ERR_SHAPE;
-    return 0;
-}
-
 extern "C" int nrv_conv_unfold(const void* src, int src_dtype, int src_layout, void* cols_bf16,
                                int B, int C, int H, int W, int ks, int stride, int pad, void* stream) {
-    ConvGeom g{};
-    if (conv_geom(g, B, C, H, W, ks, stride, pad)) return NRV_ERR_SHAPE;
+    UnfoldGeom g{};
+    if (unfold_geom(g, B, C, H, W, ks, stride, pad, C)) return NRV_ERR_SHAPE;
     if (!src || !cols_bf16) return NRV_ERR_NULL;
     if (src_layout != NRV_CONV_NCHW && src_layout != NRV_CONV_NHWC) return NRV_ERR_SHAPE;
     if (src_dtype != NRV_F32 && src_dtype != NRV_BF16) return NRV_ERR_DTYPE;
     if (src_layout == NRV_CONV_NHWC && src_dtype != NRV_BF16) return NRV_ERR_DTYPE;
     if (!nrv_aligned16(cols_bf16) || (src_layout == NRV_CONV_NHWC && !nrv_aligned16(src))) return NRV_ERR_ALIGN;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int grid = grid_for((long long)B * g.Ho * g.Wo * (g.KP >> 3), 256);
-    bf16_t* out = static_cast<bf16_t*>(cols_bf16);
-    if (src_layout == NRV_CONV_NHWC) hipLaunchKernelGGL((conv_unfold_kernel<2>), dim3(grid), dim3(256), 0, s, src, out, g);
-    else if (src_dtype == NRV_F32) hipLaunchKernelGGL((conv_unfold_kernel<0>), dim3(grid), dim3(256), 0, s, src, out, g);
-    else hipLaunchKernelGGL((conv_unfold_kernel<1>), dim3(grid), dim3(256), 0, s, src, out, g);
+    launch_unfold<UF_TAP_MAJOR>(src_layout == NRV_CONV_NHWC, src_dtype == NRV_F32, src, cols_bf16, g, CONV_GRID_CAP, static_cast<hipStream_t>(stream));
     NRV_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" int nrv_conv_fold(const void* dcols_bf16, float* dx, int B, int C, int H, int W, int ks, int stride, int pad, void* stream) {
-    ConvGeom g{};
-    if (conv_geom(g, B, C, H, W, ks, stride, pad)) return NRV_ERR_SHAPE;
+    UnfoldGeom g{};
+    if (unfold_geom(g, B, C, H, W, ks, stride, pad, C)) return NRV_ERR_SHAPE;
     if (!dcols_bf16 || !dx) return NRV_ERR_NULL;
-    hipLaunchKernelGGL(conv_fold_kernel, dim3(grid_for((long long)B * H * W * C, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const bf16_t*>(dcols_bf16), dx, g);
+    launch_fold<UF_TAP_MAJOR, false>(dcols_bf16, dx, g, CONV_GRID_CAP, static_cast<hipStream_t>(stream));
+    NRV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nrv_soft_split_fwd(const void* src, int src_dtype, int src_layout, int64_t ld_src, void* cols_bf16,
+                                  int B, int C, int H, int W, int ks, int stride, int pad, void* stream) {
+    UnfoldGeom g{};
+    if (unfold_geom(g, B, C, H, W, ks, stride, pad, ld_src)) return NRV_ERR_SHAPE;
+    if (src_layout != NRV_SPLIT_NCHW && src_layout != NRV_SPLIT_ROWS) return NRV_ERR_SHAPE;
+    if (src_layout == NRV_SPLIT_ROWS && ld_src < C) return NRV_ERR_SHAPE;
+    if (!src || !cols_bf16) return NRV_ERR_NULL;
+    if (src_dtype != NRV_F32 && src_dtype != NRV_BF16) return NRV_ERR_DTYPE;
+    if (src_layout == NRV_SPLIT_ROWS && src_dtype != NRV_BF16) return NRV_ERR_DTYPE;
+    if (!nrv_aligned16(cols_bf16)) return NRV_ERR_ALIGN;
+    launch_unfold<UF_CHANNEL_MAJOR>(src_layout == NRV_SPLIT_ROWS, src_dtype == NRV_F32, src, cols_bf16, g, SPLIT_GRID_CAP, static_cast<hipStream_t>(stream));
+    NRV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nrv_soft_split_bwd(const void* dcols_bf16, float* dx, int64_t ld_dx, int B, int C, int H, int W, int ks, int stride,
+                                  int pad, void* stream) {
+    UnfoldGeom g{};
+    if (unfold_geom(g, B, C, H, W, ks, stride, pad, ld_dx)) return NRV_ERR_SHAPE;
+    if (ld_dx < C) return NRV_ERR_SHAPE;
+    if (!dcols_bf16 || !dx) return NRV_ERR_NULL;
+    launch_fold<UF_CHANNEL_MAJOR, true>(dcols_bf16, dx, g, SPLIT_GRID_CAP, static_cast<hipStream_t>(stream));
     NRV_CHECK_LAUNCH();
     return 0;
 }
@@ -434,7 +491,7 @@ extern "C" int nrv_cast_f32_bf16(const float* x, void* y_bf16, int64_t n, void* 
     if (n <= 0) return NRV_ERR_SHAPE;
     if (!nrv_aligned16(x) || !nrv_aligned16(y_bf16)) return NRV_ERR_ALIGN;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(cast_kernel, dim3(grid_for(n >> 2, 256)), dim3(256), 0, s, x, static_cast<bf16_t*>(y_bf16), (long long)n);
+    hipLaunchKernelGGL(cast_kernel, dim3(grid_for(n >> 2, 256, 4096)), dim3(256), 0, s, x, static_cast<bf16_t*>(y_bf16), (long long)n);
     NRV_CHECK_LAUNCH();
     return 0;
 }
@@ -444,7 +501,7 @@ extern "C" int nrv_dropout_add_f32(const float* x, const float* y, const unsigne
     if (n <= 0 || (n & 7)) return NRV_ERR_SHAPE;
     if (!nrv_aligned16(x) || !nrv_aligned16(y) || !nrv_aligned16(out) || (reinterpret_cast<uintptr_t>(keep) & 7u)) return NRV_ERR_ALIGN;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(dropout_add_kernel, dim3(grid_for(n >> 3, 256)), dim3(256), 0, s, x, y, keep, out, scale, (long long)(n >> 3));
+    hipLaunchKernelGGL(dropout_add_kernel, dim3(grid_for(n >> 3, 256, 4096)), dim3(256), 0, s, x, y, keep, out, scale, (long long)(n >> 3));
     NRV_CHECK_LAUNCH();
     return 0;
 }
@@ -454,7 +511,7 @@ extern "C" int nrv_mask_mul_bf16(const void* a_bf16, const unsigned char* keep, 
     if (n <= 0 || (n & 7)) return NRV_ERR_SHAPE;
     if (!nrv_aligned16(a_bf16) || !nrv_aligned16(out_bf16) || (reinterpret_cast<uintptr_t>(keep) & 7u)) return NRV_ERR_ALIGN;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(mask_mul_kernel, dim3(grid_for(n >> 3, 256)), dim3(256), 0, s, static_cast<const bf16_t*>(a_bf16), keep,
+    hipLaunchKernelGGL(mask_mul_kernel, dim3(grid_for(n >> 3, 256, 4096)), dim3(256), 0, s, static_cast<const bf16_t*>(a_bf16), keep,
                        static_cast<bf16_t*>(out_bf16), scale, (long long)(n >> 3));
     NRV_CHECK_LAUNCH();
     return 0;
@@ -464,7 +521,7 @@ extern "C" int nrv_mask_mul_f32(const float* a, const unsigned char* keep, float
     if (!a || !keep || !out) return NRV_ERR_NULL;
     if (n <= 0) return NRV_ERR_SHAPE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(mask_mul_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, a, keep, out, scale, (long long)n);
+    hipLaunchKernelGGL(mask_mul_f32_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, s, a, keep, out, scale, (long long)n);
     NRV_CHECK_LAUNCH();
     return 0;
 }
@@ -475,7 +532,7 @@ extern "C" int nrv_gather_rows_f32(const float* src, const int64_t* index, float
     if (rows_out <= 0 || rows_src <= 0 || dim <= 0 || (dim & 3)) return NRV_ERR_SHAPE;
     if (!nrv_aligned16(src) || !nrv_aligned16(out)) return NRV_ERR_ALIGN;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL((move_rows_kernel<false>), dim3(grid_for(rows_out, 4)), dim3(256), 0, s,
+    hipLaunchKernelGGL((move_rows_kernel<false>), dim3(grid_for(rows_out, 4, 4096)), dim3(256), 0, s,
                        src, reinterpret_cast<const long long*>(index), out, (long long)rows_out, (long long)rows_src, dim);
     NRV_CHECK_LAUNCH();
     return 0;
@@ -487,7 +544,7 @@ extern "C" int nrv_scatter_rows_f32(const float* dout, const int64_t* index, flo
     if (rows_out <= 0 || rows_src <= 0 || dim <= 0 || (dim & 3)) return NRV_ERR_SHAPE;
     if (!nrv_aligned16(dout) || !nrv_aligned16(dsrc)) return NRV_ERR_ALIGN;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL((move_rows_kernel<true>), dim3(grid_for(rows_out, 4)), dim3(256), 0, s,
+    hipLaunchKernelGGL((move_rows_kernel<true>), dim3(grid_for(rows_out, 4, 4096)), dim3(256), 0, s,
                        dout, reinterpret_cast<const long long*>(index), dsrc, (long long)rows_out, (long long)rows_src, dim);
     NRV_CHECK_LAUNCH();
     return 0;

@@ -1,30 +1,20 @@
 // PatchConvNet kernels (gfx950): depthwise 3x3 convolution with GELU and the squeeze as a by-product, squeeze-and-excitation,
 // LayerScale residuals with row-mode drop path, the GELU' multiply of the stem, and class attention (one query per sample).
 // Token-major rows [B*H*W, C] throughout: row b*H*W + y*W + x is the reference's x.transpose(-1, -2).reshape(B, C, H, W)
-// (patch_convnet.py:239-243).  Every reduction runs in a fixed order (no atomics): reruns are bit-identical.
-#include "nrv_common.hpp"
+// (patch_convnet.py:239-243).  Every reduction runs in a fixed order (no atomics): reruns are bit-identical.  The 4- and 8-element
+// bf16 <-> fp32 row accesses (load_row / store_row) and the 256-thread LDS tree (block_sum_256 / block_max_256) are those of
+// nrv_rows.hpp.
+#include "nrv_rows.hpp"
 
 namespace {
 
-int grid_for(long long items, int block) {
-    long long g = (items + block - 1) / block;
-    return (int)(g < 1 ? 1 : (g > 65535 * 8 ? 65535 * 8 : g));
-}
-
-// four consecutive bf16 (8 bytes) <-> fp32
-__device__ __forceinline__ void ld4(const bf16_t* p, float (&v)[4]) {
-    const u32x2_t u = *reinterpret_cast<const u32x2_t*>(p);
-    v[0] = bf16lo_to_f32(u[0]); v[1] = bf16hi_to_f32(u[0]); v[2] = bf16lo_to_f32(u[1]); v[3] = bf16hi_to_f32(u[1]);
-}
-__device__ __forceinline__ void st4(bf16_t* p, const float (&v)[4]) {
-    *reinterpret_cast<u32x2_t*>(p) = u32x2_t{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
-}
+constexpr int PCN_GRID_CAP = 65535 * 8;     // workgroups of the grid-stride elementwise kernels, at most
 
 // gelu' of element (m, n) from a saved stream: bf16 [rows, ld], or the 8-bit stream of NRV_EPI_BIAS_GELU_Q8 stored in row pairs,
 // byte (m, n) at (m >> 1) * 2 ld + (n >> 6) * 128 + (m & 1) * 64 + (n & 63) (include/nrv.h).  Four columns n .. n + 3, n % 4 == 0.
 __device__ __forceinline__ void dgelu4(const void* g, int dtype, long long m, int n, int ld, float (&out)[4]) {
     if (dtype == NRV_BF16) {
-        ld4(static_cast<const bf16_t*>(g) + m * ld + n, out);
+        load_row(static_cast<const bf16_t*>(g) + m * ld + n, out);
         return;
     }
     const unsigned char* q = static_cast<const unsigned char*>(g) + (m >> 1) * 2 * (long long)ld + (n >> 6) * 128 + (m & 1) * 64 + (n & 63);
@@ -46,7 +36,7 @@ __device__ __forceinline__ void dw_taps(const bf16_t* __restrict__ a, long long 
     for (int t = 0; t < 9; ++t) {
         const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
         if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
-            ld4(a + (row0 + yy * W + xx) * C + c0, tap[t]);
+            load_row(a + (row0 + yy * W + xx) * C + c0, tap[t]);
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) tap[t][j] = 0.f;
@@ -84,7 +74,7 @@ __global__ __launch_bounds__(256) void dw_fwd_kernel(const bf16_t* __restrict__ 
                 o[j] = gelu_fwd(u);
                 acc[j] += o[j];
             }
-            st4(d + (row0 + p) * C + c0, o);
+            store_row(d + (row0 + p) * C + c0, o);
         }
     }
 #pragma unroll
@@ -127,7 +117,7 @@ __global__ __launch_bounds__(256) void dw_bwd_dd_kernel(const bf16_t* __restrict
             const int y = p / W, x = p - y * W;
             float tap[9][4], g[4];
             dw_taps(a, row0, y, x, H, W, C, c0, tap);
-            ld4(dg + (row0 + p) * C + c0, g);
+            load_row(dg + (row0 + p) * C + c0, g);
             f32x4_t o;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -182,7 +172,7 @@ __global__ __launch_bounds__(256) void dw_bwd_da_kernel(const float* __restrict_
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] *= g[j];
         }
-        st4(da + r * C + c0, o);
+        store_row(da + r * C + c0, o);
     }
 }
 
@@ -237,11 +227,11 @@ __global__ __launch_bounds__(256) void se_apply_kernel(const bf16_t* __restrict_
         const int c0 = (int)(i - r * C4) * 4;
         const long long b = r / HW;
         float v[4];
-        ld4(d + r * C + c0, v);
+        load_row(d + r * C + c0, v);
         const f32x4_t sc = *reinterpret_cast<const f32x4_t*>(s + b * C + c0);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] *= sc[j];
-        st4(g + r * C + c0, v);
+        store_row(g + r * C + c0, v);
     }
 }
 
@@ -255,8 +245,8 @@ __global__ __launch_bounds__(256) void se_dsum_kernel(const bf16_t* __restrict__
     if (c0 < C) {
         for (int p = rg; p < HW; p += DW_RG) {
             float x[4], y[4];
-            ld4(dg + ((long long)b * HW + p) * C + c0, x);
-            ld4(d + ((long long)b * HW + p) * C + c0, y);
+            load_row(dg + ((long long)b * HW + p) * C + c0, x);
+            load_row(d + ((long long)b * HW + p) * C + c0, y);
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[j] = fmaf(x[j], y[j], acc[j]);
         }
@@ -401,7 +391,7 @@ __global__ __launch_bounds__(256) void dgelu_rows_kernel(const float* __restrict
         dgelu4(gs, gdtype, r, c0, C, g);
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = v[j] * g[j];
-        st4(out + r * C + c0, o);
+        store_row(out + r * C + c0, o);
     }
 }
 
@@ -424,42 +414,6 @@ __device__ __forceinline__ const bf16_t* ca_row(const bf16_t* c, long long ldc, 
     return j == 0 ? c + (long long)b * ldc + hoff : p + ((long long)b * Np + j - 1) * ldp + hoff;
 }
 
-__device__ __forceinline__ void ld8f(const bf16_t* p, float (&v)[8]) {
-    const u32x4_t u = *reinterpret_cast<const u32x4_t*>(p);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        v[2 * k] = bf16lo_to_f32(u[k]);
-        v[2 * k + 1] = bf16hi_to_f32(u[k]);
-    }
-}
-__device__ __forceinline__ void st8f(bf16_t* p, const float (&v)[8]) {
-    *reinterpret_cast<u32x4_t*>(p) = u32x4_t{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
-}
-
-// fixed-order block reductions over 256 threads (tree in LDS)
-__device__ __forceinline__ float block_max(float v, float* buf) {
-    buf[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) buf[threadIdx.x] = fmaxf(buf[threadIdx.x], buf[threadIdx.x + o]);
-        __syncthreads();
-    }
-    const float r = buf[0];
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ float block_sum(float v, float* buf) {
-    buf[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) buf[threadIdx.x] += buf[threadIdx.x + o];
-        __syncthreads();
-    }
-    const float r = buf[0];
-    __syncthreads();
-    return r;
-}
-
 // o[e] = sum_j w[j] x_j[e] for the dh elements of one head (x = v or k rows), groups of dh/8 lanes, partials summed in order
 __device__ __forceinline__ void ca_weighted_rows(const float* w, const bf16_t* c, long long ldc, const bf16_t* p, long long ldp, int b, int Np,
                                                  int Nk, int hoff, int dh, float mul, float* part, bf16_t* out) {
@@ -469,7 +423,7 @@ __device__ __forceinline__ void ca_weighted_rows(const float* w, const bf16_t* c
     if (g < ng) {
         for (int j = g; j < Nk; j += ng) {
             float x[8];
-            ld8f(ca_row(c, ldc, p, ldp, b, Np, j, hoff) + e0, x);
+            load_row(ca_row(c, ldc, p, ldp, b, Np, j, hoff) + e0, x);
             const float wj = w[j];
 #pragma unroll
             for (int k = 0; k < 8; ++k) acc[k] = fmaf(wj, x[k], acc[k]);
@@ -486,7 +440,7 @@ __device__ __forceinline__ void ca_weighted_rows(const float* w, const bf16_t* c
             for (int r = 0; r < ng; ++r) v += part[r * dh + threadIdx.x * 8 + k];
             o[k] = v * mul;
         }
-        st8f(out + threadIdx.x * 8, o);
+        store_row(out + threadIdx.x * 8, o);
     }
 }
 
@@ -501,7 +455,7 @@ __global__ __launch_bounds__(256) void cls_attn_fwd_kernel(ClsArgs A, bf16_t* __
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int e = lane * 8 + 512 * i;
-        if (e < dh) ld8f(A.q + (long long)b * A.ldq + hoff + e, qv[i]);
+        if (e < dh) load_row(A.q + (long long)b * A.ldq + hoff + e, qv[i]);
     }
     for (int j = wv; j < Nk; j += 4) {
         const bf16_t* kr = ca_row(A.kc, A.ldkc, A.kp, A.ldkp, b, A.Np, j, hoff);
@@ -511,7 +465,7 @@ __global__ __launch_bounds__(256) void cls_attn_fwd_kernel(ClsArgs A, bf16_t* __
             const int e = lane * 8 + 512 * i;
             if (e < dh) {
                 float k[8];
-                ld8f(kr + e, k);
+                load_row(kr + e, k);
 #pragma unroll
                 for (int t = 0; t < 8; ++t) v = fmaf(qv[i][t], k[t], v);
             }
@@ -522,10 +476,10 @@ __global__ __launch_bounds__(256) void cls_attn_fwd_kernel(ClsArgs A, bf16_t* __
     __syncthreads();
     float m = -INFINITY;
     for (int j = threadIdx.x; j < Nk; j += 256) m = fmaxf(m, S[j]);
-    m = block_max(m, buf);
+    m = block_max_256(m, buf);
     float l = 0.f;
     for (int j = threadIdx.x; j < Nk; j += 256) l += __expf(S[j] - m);
-    l = block_sum(l, buf);
+    l = block_sum_256(l, buf);
     const float L = m + __logf(l);
     for (int j = threadIdx.x; j < Nk; j += 256) S[j] = __expf(S[j] - L);
     if (threadIdx.x == 0) lse[bh] = L;
@@ -549,8 +503,8 @@ __global__ __launch_bounds__(256) void cls_attn_bwd_kernel(ClsArgs A, const bf16
     for (int i = 0; i < 2; ++i) {
         const int e = lane * 8 + 512 * i;
         if (e < dh) {
-            ld8f(A.q + (long long)b * A.ldq + hoff + e, qv[i]);
-            ld8f(dout + (long long)b * ldo + hoff + e, gv[i]);
+            load_row(A.q + (long long)b * A.ldq + hoff + e, qv[i]);
+            load_row(dout + (long long)b * ldo + hoff + e, gv[i]);
         }
     }
     // P_j (recomputed from the saved lse) and dP_j = do . v_j
@@ -563,8 +517,8 @@ __global__ __launch_bounds__(256) void cls_attn_bwd_kernel(ClsArgs A, const bf16
             const int e = lane * 8 + 512 * i;
             if (e < dh) {
                 float k[8], v[8];
-                ld8f(kr + e, k);
-                ld8f(vr + e, v);
+                load_row(kr + e, k);
+                load_row(vr + e, v);
 #pragma unroll
                 for (int t = 0; t < 8; ++t) {
                     s = fmaf(qv[i][t], k[t], s);
@@ -582,7 +536,7 @@ __global__ __launch_bounds__(256) void cls_attn_bwd_kernel(ClsArgs A, const bf16
     __syncthreads();
     float D = 0.f;
     for (int j = threadIdx.x; j < Nk; j += 256) D = fmaf(P[j], dS[j], D);
-    D = block_sum(D, buf);
+    D = block_sum_256(D, buf);
     for (int j = threadIdx.x; j < Nk; j += 256) dS[j] = P[j] * (dS[j] - D);
     __syncthreads();
     // dk_j = scale dS_j q, dv_j = P_j do
@@ -600,8 +554,8 @@ __global__ __launch_bounds__(256) void cls_attn_bwd_kernel(ClsArgs A, const bf16
                     k[t] = ks * qv[i][t];
                     v[t] = pj * gv[i][t];
                 }
-                st8f(kr + e, k);
-                st8f(vr + e, v);
+                store_row(kr + e, k);
+                store_row(vr + e, v);
             }
         }
     }
@@ -658,10 +612,10 @@ extern "C" int nrv_dwconv3x3_bwd(const void* a, const float* w, const float* bia
                        static_cast<const bf16_t*>(dg), s, dmean, 1.0f / (float)(H * W), dd, part, H, W, C);
     NRV_CHECK_LAUNCH();
     const long long n4 = (long long)B * H * W * C / 4;
-    hipLaunchKernelGGL(dw_bwd_da_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, st, dd, w, gelu_stream, gelu_dtype,
+    hipLaunchKernelGGL(dw_bwd_da_kernel, dim3(grid_for(n4, 256, PCN_GRID_CAP)), dim3(256), 0, st, dd, w, gelu_stream, gelu_dtype,
                        static_cast<bf16_t*>(da_bf16), n4, H, W, C);
     NRV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dw_bwd_wred_kernel, dim3(grid_for((long long)C * 10, 256)), dim3(256), 0, st, part, dw, db, B, C);
+    hipLaunchKernelGGL(dw_bwd_wred_kernel, dim3(grid_for((long long)C * 10, 256, PCN_GRID_CAP)), dim3(256), 0, st, part, dw, db, B, C);
     NRV_CHECK_LAUNCH();
     return 0;
 }
@@ -684,7 +638,7 @@ extern "C" int nrv_se_apply(const void* d, const float* s, void* g_bf16, int B, 
     if (B <= 0 || HW <= 0 || C <= 0 || C % 8) return NRV_ERR_SHAPE;
     if (!nrv_aligned16(d) || !nrv_aligned16(s) || !nrv_aligned16(g_bf16)) return NRV_ERR_ALIGN;
     const long long n4 = (long long)B * HW * C / 4;
-    hipLaunchKernelGGL(se_apply_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(se_apply_kernel, dim3(grid_for(n4, 256, PCN_GRID_CAP)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const bf16_t*>(d), s, static_cast<bf16_t*>(g_bf16), n4, HW, C);
     NRV_CHECK_LAUNCH();
     return 0;
@@ -729,7 +683,7 @@ extern "C" int nrv_ls_add_f32(const float* x, const float* y, const float* gamma
     if (int e = ls_check(rows, rows_per_sample, C, keep, survival)) return e;
     if (!nrv_aligned16(x) || !nrv_aligned16(y) || !nrv_aligned16(gamma) || !nrv_aligned16(out)) return NRV_ERR_ALIGN;
     const long long n4 = rows * (long long)C / 4;
-    hipLaunchKernelGGL(ls_add_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, gamma, keep,
+    hipLaunchKernelGGL(ls_add_kernel, dim3(grid_for(n4, 256, PCN_GRID_CAP)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, gamma, keep,
                        keep ? 1.0f / survival : 1.0f, out, n4, keep ? (long long)rows_per_sample : 1ll, C);
     NRV_CHECK_LAUNCH();
     return 0;
@@ -765,7 +719,7 @@ extern "C" int nrv_dgelu_rows(const float* dx, const void* gelu_stream, int gelu
     if (rows <= 0 || C <= 0 || C % 8 || (gelu_dtype == NRV_U8 && C % 64)) return NRV_ERR_SHAPE;
     if (!nrv_aligned16(dx) || !nrv_aligned16(gelu_stream) || !nrv_aligned16(out_bf16)) return NRV_ERR_ALIGN;
     const long long n4 = rows * (long long)C / 4;
-    hipLaunchKernelGGL(dgelu_rows_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), dx, gelu_stream,
+    hipLaunchKernelGGL(dgelu_rows_kernel, dim3(grid_for(n4, 256, PCN_GRID_CAP)), dim3(256), 0, static_cast<hipStream_t>(stream), dx, gelu_stream,
                        gelu_dtype, static_cast<bf16_t*>(out_bf16), n4, C);
     NRV_CHECK_LAUNCH();
     return 0;

@@ -1,101 +1,13 @@
 // Tokens-to-token (T2T-ViT, t2t.py:58-93) pieces that the ViT kernels do not cover:
-//   soft split : nn.Unfold(ks, stride, pad) on token-major rows.  src = NCHW image (fp32 | bf16) or bf16 token rows
-//                [B*H*W, ld_src] (the 'b (h w) c -> b c h w' of RearrangeImage is the addressing) -> cols bf16 [B*Ho*Wo, KP],
-//                feature c*ks*ks + ky*ks + kx (nn.Unfold's channel-major order), KP = ks*ks*C rounded up to 8; taps outside
-//                the image and columns >= ks*ks*C are zero.  One thread = 8 consecutive output features, one 16-byte store.
-//   its backward: a fold in gather form.  dx[(b, y, x), c] = sum over the windows (oy, ox) that cover (y, x) of
-//                dcols[(b, oy, ox), c*ks*ks + ky*ks + kx], ky then kx ascending: at most ceil(ks / stride)^2 terms in a fixed
-//                order, fp32, no scatter, no atomics.  Columns C .. ld_dx - 1 of dx are written as zeros.
+//   soft split : nn.Unfold(ks, stride, pad) on token-major rows and its backward are the channel-major instantiation of the
+//                unfold / fold kernel pair of nrv_misc.hip (nrv_soft_split_fwd / nrv_soft_split_bwd live there).
 //   LayerNorm over the true width n of rows stored with a stride ld >= n (n = 147, 1323: ks*ks*C is no multiple of 8, the
 //                GEMMs need K % 8 == 0, so the residual stream keeps zero pad columns): statistics over n, pad columns of
 //                y / dx written as zeros.  One wave per row, two passes over the row for mean and centred variance (the
 //                second pass hits L1 / L2).  dgamma / dbeta: per-slab column sums, then a finalize in slab order.
-#include "nrv_common.hpp"
+#include "nrv_rows.hpp"
 
 namespace {
-
-struct SplitGeom {
-    int B, C, H, W, Ho, Wo, ks, stride, pad, KP;
-    long long ld;            // row stride of the token-row source (forward) / of dx (backward)
-};
-
-template <int SRC>      // 0: NCHW fp32, 1: NCHW bf16, 2: bf16 token rows [B*H*W, ld]
-__device__ __forceinline__ bf16_t split_src(const void* src, const SplitGeom& g, int b, int c, int iy, int ix) {
-    if (SRC == 0) return f32_to_bf16(reinterpret_cast<const float*>(src)[(((long long)b * g.C + c) * g.H + iy) * g.W + ix]);
-    if (SRC == 1) return reinterpret_cast<const bf16_t*>(src)[(((long long)b * g.C + c) * g.H + iy) * g.W + ix];
-    return reinterpret_cast<const bf16_t*>(src)[(((long long)b * g.H + iy) * g.W + ix) * g.ld + c];
-}
-
-template <int SRC>
-__global__ __launch_bounds__(256) void soft_split_kernel(const void* __restrict__ src, bf16_t* __restrict__ out, SplitGeom g) {
-    const int kk = g.ks * g.ks, F = kk * g.C, F8 = g.KP >> 3;
-    const long long total = (long long)g.B * g.Ho * g.Wo * F8;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const long long t = i / F8;
-        const int f0 = (int)(i - t * F8) * 8;
-        const int b = (int)(t / ((long long)g.Ho * g.Wo));
-        const int rem = (int)(t - (long long)b * g.Ho * g.Wo);
-        const int oy = rem / g.Wo, ox = rem - (rem / g.Wo) * g.Wo;
-        unsigned v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int f = f0 + j;
-            const int c = f / kk, k = f - c * kk;
-            const int ky = k / g.ks, kx = k - ky * g.ks;
-            const int iy = oy * g.stride - g.pad + ky, ix = ox * g.stride - g.pad + kx;
-            v[j] = (f < F && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W) ? split_src<SRC>(src, g, b, c, iy, ix) : 0u;
-        }
-        u32x4_t pk = {v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)};
-        *reinterpret_cast<u32x4_t*>(out + t * g.KP + f0) = pk;
-    }
-}
-
-__global__ __launch_bounds__(256) void soft_split_bwd_kernel(const bf16_t* __restrict__ dcols, float* __restrict__ dx, SplitGeom g) {
-    const int kk = g.ks * g.ks;
-    const long long total = (long long)g.B * g.H * g.W * g.ld;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const long long pix = i / g.ld;
-        const int c = (int)(i - pix * g.ld);
-        float acc = 0.f;
-        if (c < g.C) {
-            const int b = (int)(pix / ((long long)g.H * g.W));
-            const int rem = (int)(pix - (long long)b * g.H * g.W);
-            const int y = rem / g.W, x = rem - (rem / g.W) * g.W;
-            for (int ky = 0; ky < g.ks; ++ky) {
-                const int ny = y + g.pad - ky;
-                if (ny < 0 || ny % g.stride) continue;
-                const int oy = ny / g.stride;
-                if (oy >= g.Ho) continue;
-                for (int kx = 0; kx < g.ks; ++kx) {
-                    const int nx = x + g.pad - kx;
-                    if (nx < 0 || nx % g.stride) continue;
-                    const int ox = nx / g.stride;
-                    if (ox >= g.Wo) continue;
-                    acc += bf16_to_f32(dcols[(((long long)b * g.Ho + oy) * g.Wo + ox) * g.KP + c * kk + ky * g.ks + kx]);
-                }
-            }
-        }
-        dx[i] = acc;
-    }
-}
-
-int grid_for(long long work_items, int block, int cap) {
-    long long g = (work_items + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
-int split_geom(SplitGeom& g, int B, int C, int H, int W, int ks, int stride, int pad, long long ld) {
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ks <= 0 || ks > 7 || stride <= 0 || pad < 0 || pad >= ks) return NRV_ERR_SHAPE;
-    if (H + 2 * pad < ks || W + 2 * pad < ks) return NRV_ERR_SHAPE;
-    g.B = B; g.C = C; g.H = H; g.W = W; g.ks = ks; g.stride = stride; g.pad = pad; g.ld = ld;
-    g.Ho = (H + 2 * pad - ks) / stride + 1;
-    g.Wo = (W + 2 * pad - ks) / stride + 1;
-    g.KP = (ks * ks * C + 7) & ~7;
-    if ((long long)B * g.Ho * g.Wo * g.KP > (1ll << 40) || (long long)B * H * W * (ld > C ? ld : C) > (1ll << 40)) return NRV_ERR_SHAPE;
-    return 0;
-}
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm over n of ld columns
@@ -219,38 +131,6 @@ int lnp_shape(long long rows, int n, long long ld) {
 }
 
 }  // namespace
-
-extern "C" int nrv_soft_split_fwd(const void* src, int src_dtype, int src_layout, int64_t ld_src, void* cols_bf16,
-                                  int B, int C, int H, int W, int ks, int stride, int pad, void* stream) {
-    SplitGeom g{};
-    if (split_geom(g, B, C, H, W, ks, stride, pad, ld_src)) return NRV_ERR_SHAPE;
-    if (src_layout != NRV_SPLIT_NCHW && src_layout != NRV_SPLIT_ROWS) return NRV_ERR_SHAPE;
-    if (src_layout == NRV_SPLIT_ROWS && ld_src < C) return NRV_ERR_SHAPE;
-    if (!src || !cols_bf16) return NRV_ERR_NULL;
-    if (src_dtype != NRV_F32 && src_dtype != NRV_BF16) return NRV_ERR_DTYPE;
-    if (src_layout == NRV_SPLIT_ROWS && src_dtype != NRV_BF16) return NRV_ERR_DTYPE;
-    if (!nrv_aligned16(cols_bf16)) return NRV_ERR_ALIGN;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int grid = grid_for((long long)B * g.Ho * g.Wo * (g.KP >> 3), 256, 16384);
-    bf16_t* out = static_cast<bf16_t*>(cols_bf16);
-    if (src_layout == NRV_SPLIT_ROWS) hipLaunchKernelGGL((soft_split_kernel<2>), dim3(grid), dim3(256), 0, s, src, out, g);
-    else if (src_dtype == NRV_F32) hipLaunchKernelGGL((soft_split_kernel<0>), dim3(grid), dim3(256), 0, s, src, out, g);
-    else hipLaunchKernelGGL((soft_split_kernel<1>), dim3(grid), dim3(256), 0, s, src, out, g);
-    NRV_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int nrv_soft_split_bwd(const void* dcols_bf16, float* dx, int64_t ld_dx, int B, int C, int H, int W, int ks, int stride,
-                                  int pad, void* stream) {
-    SplitGeom g{};
-    if (split_geom(g, B, C, H, W, ks, stride, pad, ld_dx)) return NRV_ERR_SHAPE;
-    if (ld_dx < C) return NRV_ERR_SHAPE;
-    if (!dcols_bf16 || !dx) return NRV_ERR_NULL;
-    hipLaunchKernelGGL(soft_split_bwd_kernel, dim3(grid_for((long long)B * H * W * ld_dx, 256, 16384)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(dcols_bf16), dx, g);
-    NRV_CHECK_LAUNCH();
-    return 0;
-}
 
 extern "C" int nrv_layernorm_pad_fwd(const void* x, int x_dtype, const float* gamma, const float* beta, void* y_bf16, float* mean,
                                      float* rstd, int64_t rows, int n, int64_t ld, float eps, void* stream) {

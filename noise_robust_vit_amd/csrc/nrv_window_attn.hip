@@ -14,9 +14,11 @@
 //             steps through an LDS column sum); dS = P0 (G - rowsum(G P0)); dQ_i in-lane; then P and dS go to LDS and lane j
 //             forms dK_j = scale dS^T Q and dV_j = P^T dO.  The relative-position-table gradient is dS folded through the index:
 //             each workgroup sums it over a fixed chunk of WA_CHUNK windows of one head in registers and writes one partial per
-//             table entry; a second kernel adds the partials of each entry in a fixed order.  No atomics: bit-reproducible.
-// Nothing [windows, H, N, N]-sized reaches HBM.
-#include "nrv_common.hpp"
+//             table entry; reduce_partials_kernel (nrv_rows.hpp) adds the partials of each entry in a fixed order.  No atomics:
+//             bit-reproducible.
+// Nothing [windows, H, N, N]-sized reaches HBM.  The row helpers (load_row / dot_row / axpy_row / store_row, on global and LDS rows)
+// are those of nrv_rows.hpp.
+#include "nrv_rows.hpp"
 
 #include <cmath>
 
@@ -68,62 +70,10 @@ __device__ __forceinline__ int slot_region(const WinParams& p, long long win, in
 }
 
 template <int DH>
-__device__ __forceinline__ void load_row_f32(const bf16_t* src, bool ok, float (&r)[DH]) {
-#pragma unroll
-    for (int c = 0; c < DH / 8; ++c) {
-        const u32x4_t v = ok ? *reinterpret_cast<const u32x4_t*>(src + c * 8) : u32x4_t{0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            r[c * 8 + 2 * e] = bf16lo_to_f32(v[e]);
-            r[c * 8 + 2 * e + 1] = bf16hi_to_f32(v[e]);
-        }
-    }
-}
-
-template <int DH>
 __device__ __forceinline__ void copy_row_lds(const bf16_t* src, bool ok, bf16_t* dst) {
 #pragma unroll
     for (int c = 0; c < DH / 8; ++c)
         *reinterpret_cast<u32x4_t*>(dst + c * 8) = ok ? *reinterpret_cast<const u32x4_t*>(src + c * 8) : u32x4_t{0u, 0u, 0u, 0u};
-}
-
-template <int DH>
-__device__ __forceinline__ float dot_lds(const float (&a)[DH], const bf16_t* row) {
-    float acc = 0.f;
-#pragma unroll
-    for (int c = 0; c < DH / 8; ++c) {
-        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(row + c * 8);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            acc = fmaf(a[c * 8 + 2 * e], bf16lo_to_f32(v[e]), acc);
-            acc = fmaf(a[c * 8 + 2 * e + 1], bf16hi_to_f32(v[e]), acc);
-        }
-    }
-    return acc;
-}
-
-template <int DH>
-__device__ __forceinline__ void axpy_lds(float w, const bf16_t* row, float (&acc)[DH]) {
-#pragma unroll
-    for (int c = 0; c < DH / 8; ++c) {
-        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(row + c * 8);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            acc[c * 8 + 2 * e] = fmaf(w, bf16lo_to_f32(v[e]), acc[c * 8 + 2 * e]);
-            acc[c * 8 + 2 * e + 1] = fmaf(w, bf16hi_to_f32(v[e]), acc[c * 8 + 2 * e + 1]);
-        }
-    }
-}
-
-template <int DH>
-__device__ __forceinline__ void store_row_bf16(bf16_t* dst, const float (&r)[DH], float mul) {
-#pragma unroll
-    for (int c = 0; c < DH / 8; ++c) {
-        u32x4_t v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = pack_bf16x2(r[c * 8 + 2 * e] * mul, r[c * 8 + 2 * e + 1] * mul);
-        *reinterpret_cast<u32x4_t*>(dst + c * 8) = v;
-    }
 }
 
 // score of lane i's query against key j (j < N): (scale q_i) . k_j + table[rel(i, j)] (+ -100 across shift regions).
@@ -147,7 +97,7 @@ template <int DH>
 __device__ __forceinline__ float score(const WinParams& p, long long win, const ScoreCtx& c, int j, const float (&q)[DH],
                                        const bf16_t* sk, const float* stab) {
     const int yj = j / p.Ww, xj = j - yj * p.Ww;
-    float v = dot_lds<DH>(q, sk + j * DH) + stab[c.base - (yj * c.tw + xj)];
+    float v = dot_row<DH>(q, sk + j * DH) + stab[c.base - (yj * c.tw + xj)];
     if (c.masked && slot_region(p, win, j) != c.ri) v += -100.0f;
     return v;
 }
@@ -180,7 +130,7 @@ __global__ __launch_bounds__(64) void wattn_fwd_kernel(WinParams p) {
     copy_row_lds<DH>(src + 2 * p.C, valid, sv + lane * DH);
     stage_table(p, h, stab);
     float q[DH];
-    load_row_f32<DH>(src, true, q);
+    load_row<DH>(src, q);
 #pragma unroll
     for (int d = 0; d < DH; ++d) q[d] *= p.scale;
     __syncthreads();
@@ -234,9 +184,9 @@ __global__ __launch_bounds__(64) void wattn_fwd_kernel(WinParams p) {
     for (int j = 0; j < N; ++j) {
         float w = sS[sw_idx(lane, j)];
         if constexpr (ROBUST) w *= sb[j];                          // P0 diag(b3); diag(a4) on the store
-        axpy_lds<DH>(w, sv + j * DH, o);
+        axpy_row<DH>(w, sv + j * DH, o);
     }
-    if (valid) store_row_bf16<DH>(p.o + row * p.C + h * DH, o, a);
+    if (valid) store_row<DH>(p.o + row * p.C + h * DH, o, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -287,7 +237,7 @@ __global__ __launch_bounds__(64) void wattn_bwd_kernel(WinParams p) {
         // row phase: lane i owns row i of sS / sD
         {
             float q[DH];
-            load_row_f32<DH>(src, true, q);
+            load_row<DH>(src, q);
 #pragma unroll
             for (int d = 0; d < DH; ++d) q[d] *= p.scale;
             const ScoreCtx c = score_ctx(p, win, i);
@@ -295,8 +245,8 @@ __global__ __launch_bounds__(64) void wattn_bwd_kernel(WinParams p) {
         }
         {
             float dov[DH];
-            load_row_f32<DH>(dsrc, true, dov);
-            for (int j = 0; j < N; ++j) sD[sw_idx(lane, j)] = valid ? dot_lds<DH>(dov, sv + j * DH) : 0.f;
+            load_row<DH>(dsrc, dov);
+            for (int j = 0; j < N; ++j) sD[sw_idx(lane, j)] = valid ? dot_row<DH>(dov, sv + j * DH) : 0.f;
         }
         if constexpr (ROBUST) {
             const float a4 = sat[4][i], a3 = sat[3][i];
@@ -337,10 +287,10 @@ __global__ __launch_bounds__(64) void wattn_bwd_kernel(WinParams p) {
                 const float ds = p0 * (sD[sw_idx(lane, j)] - r);
                 sD[sw_idx(lane, j)] = ds;
                 if constexpr (ROBUST) sS[sw_idx(lane, j)] = a4 * p0 * sbt[3][j];
-                axpy_lds<DH>(ds, sk + j * DH, dq);
+                axpy_row<DH>(ds, sk + j * DH, dq);
             }
         }
-        if (valid) store_row_bf16<DH>(p.dqkv + row * ld + h * DH, dq, p.scale);
+        if (valid) store_row<DH>(p.dqkv + row * ld + h * DH, dq, p.scale);
         __syncthreads();                           // K / V are dead: sX takes Q and dO
         copy_row_lds<DH>(src, valid, sX + lane * DH);
         copy_row_lds<DH>(dsrc, valid, sX + (WA_N + lane) * DH);
@@ -350,12 +300,12 @@ __global__ __launch_bounds__(64) void wattn_bwd_kernel(WinParams p) {
 #pragma unroll
             for (int d = 0; d < DH; ++d) { dk[d] = 0.f; dv[d] = 0.f; }
             for (int k = 0; k < N; ++k) {
-                axpy_lds<DH>(sD[sw_idx(k, lane)], sX + k * DH, dk);
-                axpy_lds<DH>(sS[sw_idx(k, lane)], sX + (WA_N + k) * DH, dv);
+                axpy_row<DH>(sD[sw_idx(k, lane)], sX + k * DH, dk);
+                axpy_row<DH>(sS[sw_idx(k, lane)], sX + (WA_N + k) * DH, dv);
             }
             if (valid) {
-                store_row_bf16<DH>(p.dqkv + row * ld + p.C + h * DH, dk, p.scale);
-                store_row_bf16<DH>(p.dqkv + row * ld + 2 * p.C + h * DH, dv, 1.f);
+                store_row<DH>(p.dqkv + row * ld + p.C + h * DH, dk, p.scale);
+                store_row<DH>(p.dqkv + row * ld + 2 * p.C + h * DH, dv, 1.f);
             }
         }
         // table gradient: entry t = (dy, dx) collects dS[i][j] over the pairs with coord_i - coord_j = (dy, dx)
@@ -382,24 +332,6 @@ __global__ __launch_bounds__(64) void wattn_bwd_kernel(WinParams p) {
     }
 }
 
-// dtable[t, h] = sum over chunks of part[h, t, chunk]: one workgroup per (t, h); thread k adds chunks k, k + 256, ... in order,
-// then a fixed tree over the 256 threads
-__global__ __launch_bounds__(256) void wattn_table_reduce_kernel(const float* __restrict__ part, float* __restrict__ dtable,
-                                                                 int T, int H, int chunks) {
-    __shared__ float red[256];
-    const int t = blockIdx.x, h = blockIdx.y;
-    const float* src = part + ((long long)h * T + t) * chunks;
-    float acc = 0.f;
-    for (int c = threadIdx.x; c < chunks; c += 256) acc += src[c];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) dtable[(long long)t * H + h] = red[0];
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // stochastic depth, row mode (torchvision StochasticDepth(p, "row"), swin.py:519,532-533): a per-sample factor keep[b] / survival
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -424,11 +356,6 @@ __global__ __launch_bounds__(256) void sd_scale_kernel(const float* __restrict__
         const f32x4_t v = *reinterpret_cast<const f32x4_t*>(dy + e * 4);
         *reinterpret_cast<u32x2_t*>(out + e * 4) = u32x2_t{pack_bf16x2(v[0] * f, v[1] * f), pack_bf16x2(v[2] * f, v[3] * f)};
     }
-}
-
-int grid_for(long long items, int block) {
-    long long g = (items + block - 1) / block;
-    return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
 }
 
 // shared argument rules of the three window entry points; fills p (pointers excepted)
@@ -461,7 +388,9 @@ template <int DH, bool R>
 int launch_bwd(const WinParams& p, float* dtable, hipStream_t s) {
     hipLaunchKernelGGL((wattn_bwd_kernel<DH, R>), dim3((unsigned)p.chunks, (unsigned)p.H), dim3(WA_N), 0, s, p);
     NRV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(wattn_table_reduce_kernel, dim3((unsigned)p.T, (unsigned)p.H), dim3(256), 0, s, p.part, dtable, p.T, p.H, p.chunks);
+    // dtable[t, h] = sum over the chunks of part[h, t, chunk]
+    hipLaunchKernelGGL((reduce_partials_kernel<256>), dim3((unsigned)p.T, (unsigned)p.H), dim3(256), 0, s, p.part, dtable, p.chunks,
+                       (long long)p.H, 1ll);
     NRV_CHECK_LAUNCH();
     return 0;
 }
@@ -526,7 +455,7 @@ extern "C" int nrv_sd_add_f32(const float* x, const float* y, const float* keep,
         return NRV_ERR_SHAPE;
     if (!nrv_aligned16(x) || !nrv_aligned16(y) || !nrv_aligned16(out) || (reinterpret_cast<uintptr_t>(keep) & 3u)) return NRV_ERR_ALIGN;
     const long long n4 = rows * (long long)dim / 4, ps4 = rows_per_sample * (long long)dim / 4;
-    hipLaunchKernelGGL(sd_add_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, keep, out, survival, n4, ps4);
+    hipLaunchKernelGGL(sd_add_kernel, dim3(grid_for(n4, 256, 4096)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, keep, out, survival, n4, ps4);
     NRV_CHECK_LAUNCH();
     return 0;
 }
@@ -538,7 +467,7 @@ extern "C" int nrv_sd_scale_bf16(const float* dy, const float* keep, void* out_b
         return NRV_ERR_SHAPE;
     if (!nrv_aligned16(dy) || (reinterpret_cast<uintptr_t>(out_bf16) & 7u) || (reinterpret_cast<uintptr_t>(keep) & 3u)) return NRV_ERR_ALIGN;
     const long long n4 = rows * (long long)dim / 4, ps4 = rows_per_sample * (long long)dim / 4;
-    hipLaunchKernelGGL(sd_scale_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), dy, keep,
+    hipLaunchKernelGGL(sd_scale_kernel, dim3(grid_for(n4, 256, 4096)), dim3(256), 0, static_cast<hipStream_t>(stream), dy, keep,
                        static_cast<bf16_t*>(out_bf16), survival, n4, ps4);
     NRV_CHECK_LAUNCH();
     return 0;

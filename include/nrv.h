@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NRV_ABI_VERSION 17
+#define NRV_ABI_VERSION 18
 
 /* dtype codes */
 #define NRV_F32 0
@@ -152,6 +152,30 @@ typedef struct nrv_tn_problem {
 size_t nrv_gemm_tn_grouped_workspace(const nrv_tn_problem* problems, int nprob, int64_t T);
 int nrv_gemm_tn_grouped_bf16(const nrv_tn_problem* problems, int nprob, int64_t T,
                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Launch-plan queries (ABI 18).  Read-only: they launch nothing, touch no device memory and are callable without a GPU (the
+ * library then plans for 256 CUs).  They report what nrv_gemm_nt_bf16 / nrv_gemm_tn_bf16 WOULD launch for the same arguments
+ * under the current nrv_set_reserved_cus() value; the launches and the queries go through one planning function, so the answer
+ * is the launch's own decision, not a copy of it.  Operand pointers, leading dimensions and dtypes do not enter a plan.
+ * Return 0 and fill *plan, or NRV_ERR_NULL / NRV_ERR_SHAPE / NRV_ERR_EPILOGUE by the rules of the launch (N % 8, K % 8, the
+ * remap only with NRV_EPI_BIAS_RESIDUAL, the _Q8 epilogues only with N % 64 == 0, beta 0 or 1).
+ *   nrv_gemm_nt_plan: `remap` != 0 when the launch passes out_group > 0 or aux_row_mod > 0.
+ *     tile_m x tile_n : the tile configuration (256 / 320 / 192 / 128 rows x 256 columns, or 384 x 128);
+ *     phased          : 1 = the phased persistent kernel (K % 64 == 0 and K >= 192: workgroup b walks the tiles b, b + grid, ...),
+ *                       0 = the plain kernel, one tile per workgroup;
+ *     tiles, grid     : output tiles and workgroups launched (grid == tiles on the plain kernel).
+ *   nrv_gemm_tn_plan: `a_group` != 0 when the launch remaps the rows of A, `dbias` != 0 when it asks for the bias gradient.
+ *     tiles           : 256 x 256 output tiles; the grid is tiles * splits workgroups;
+ *     splits, kt_q, kt_r : token splits and the K-tiles (64 token rows) of a split: kt_q, the first kt_r splits one more;
+ *     phased          : 1 = the phased kernel (no row remap and kt_q >= 3), 0 = the plain one;
+ *     direct          : 1 = one split and beta == 0: the kernel stores into C with the caller's ldc; 0 = fp32 slabs in the workspace;
+ *     reduce          : 1 = the reduction kernel runs (slabs, or the bias gradient of a direct launch).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct nrv_nt_plan { int tile_m, tile_n, phased, tiles, grid; } nrv_nt_plan;
+typedef struct nrv_tn_plan { int tiles, splits, kt_q, kt_r, phased, direct, reduce; } nrv_tn_plan;
+int nrv_gemm_nt_plan(int64_t M, int64_t N, int64_t K, int epilogue, int remap, nrv_nt_plan* plan);
+int nrv_gemm_tn_plan(int64_t M, int64_t N, int64_t T, int a_group, float beta, int dbias, nrv_tn_plan* plan);
 
 /* Column sum (bias gradient of nn.Linear's backward): out[n] = beta*out[n] + sum_t X[t,n].
  *   X bf16 [T,N] ld; N % 8 == 0.  workspace: nrv_colsum_workspace(T, N) bytes. */

@@ -18,7 +18,7 @@ LIB_PATH = _DEFAULT_LIB       # no environment override: what runs is the in-tre
 NRV_F32, NRV_BF16, NRV_U8 = 0, 1, 2
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_DGELU, EPI_BIAS_GELU_Q8, EPI_DGELU_Q8 = 0, 1, 2, 3, 4, 5, 6
 PATCH_P1P2C, PATCH_CP1P2 = 0, 1
-ABI_VERSION = 17
+ABI_VERSION = 18
 ATTN_QKV_BLOCKED, ATTN_OUT_BLOCKED = 1, 2      # include/nrv.h: NRV_ATTN_*_BLOCKED
 CONV_NCHW, CONV_NHWC = 0, 1                    # include/nrv.h: NRV_CONV_*
 SPLIT_NCHW, SPLIT_ROWS = 0, 1                  # include/nrv.h: NRV_SPLIT_*
@@ -29,6 +29,16 @@ class TnProblem(ctypes.Structure):
     """include/nrv.h `nrv_tn_problem`: one weight gradient of a grouped launch."""
     _fields_ = [("A", c_void_p), ("lda", c_int64), ("B", c_void_p), ("ldb", c_int64), ("C", c_void_p), ("ldc", c_int64),
                 ("M", c_int64), ("N", c_int64), ("beta", c_float), ("dbias", c_void_p), ("dbias_beta", c_float)]
+
+class NtPlan(ctypes.Structure):
+    """include/nrv.h `nrv_nt_plan`: what nrv_gemm_nt_bf16 would launch."""
+    _fields_ = [("tile_m", c_int), ("tile_n", c_int), ("phased", c_int), ("tiles", c_int), ("grid", c_int)]
+
+
+class TnPlan(ctypes.Structure):
+    """include/nrv.h `nrv_tn_plan`: what nrv_gemm_tn_bf16 would launch."""
+    _fields_ = [("tiles", c_int), ("splits", c_int), ("kt_q", c_int), ("kt_r", c_int), ("phased", c_int), ("direct", c_int),
+                ("reduce", c_int)]
 
 
 # name -> (restype, argtypes); every symbol include/nrv.h declares (tests/test_abi.py checks the two agree)
@@ -46,6 +56,8 @@ SIGNATURES = {
                                  c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64,
                                  c_int64, c_int64, c_int64, c_void_p]),
     "nrv_gemm_tn_workspace": (c_size_t, [c_int64, c_int64, c_int64]),
+    "nrv_gemm_nt_plan": (c_int, [c_int64, c_int64, c_int64, c_int, c_int, c_void_p]),
+    "nrv_gemm_tn_plan": (c_int, [c_int64, c_int64, c_int64, c_int, c_float, c_int, c_void_p]),
     "nrv_gemm_tn_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                  c_int64, c_int64, c_int64, c_float, c_int64, c_int64, c_int64,
                                  c_void_p, c_float, c_void_p, c_size_t, c_void_p]),

@@ -1663,34 +1663,39 @@ int set_lds(KernelT k, int bytes) {
     return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
+// The launch plan of one NT GEMM: which tile configuration, which kernel, how many tiles and workgroups.  nt_plan() below is the ONLY
+// place that decides; the launch (launch_nt) and the read-only query (nrv_gemm_nt_plan) both go through it.
+struct NtPlan {
+    int tile;               // 256 / 320 / 192 / 128 rows of a 256-column tile, or 1384 = the 384 x 128 tile
+    int tbm, tbn;           // tile rows, tile columns
+    bool phased;            // gemm_nt8_kernel (phased K loop, persistent) or gemm_nt_kernel (one tile per workgroup)
+    bool remap;             // the per-row-pointer epilogue (row scatter / operand-row broadcast): 256-row tiles, plain kernel
+    int tiles_m, tiles_n, ntiles;
+    int grid;               // workgroups launched
+};
+
 template <typename C, int EPI, bool OUT_F32, bool AUX_F32, bool REMAP>
-int launch_nt_cfg(GemmNTParams p, hipStream_t s) {
+int launch_nt_cfg(GemmNTParams p, const NtPlan& pl, hipStream_t s) {
     static int attr = set_lds(gemm_nt_kernel<C, EPI, OUT_F32, AUX_F32, REMAP>, C::LDS);
     if (attr != 0) return attr;
-    const int tiles_m = (int)nrv_cdiv(p.e.M, C::TBM), tiles_n = (int)nrv_cdiv(p.e.N, C::TBN);
-    p.tiles_n = tiles_n;
+    if (pl.tbm != C::TBM || pl.tbn != C::TBN || pl.phased) return NRV_ERR_SHAPE;      // plan / instantiation mismatch: never launched
+    p.tiles_n = pl.tiles_n;
     p.gn = 4;               // column groups of 4 tiles per XCD (swept 2, 3, 4, 6, 12, off in round 1: 8192^3 1111 -> 1336 TFLOP/s)
-    hipLaunchKernelGGL((gemm_nt_kernel<C, EPI, OUT_F32, AUX_F32, REMAP>), dim3(tiles_m * tiles_n), dim3(C::THREADS), C::LDS, s, p);
+    hipLaunchKernelGGL((gemm_nt_kernel<C, EPI, OUT_F32, AUX_F32, REMAP>), dim3(pl.grid), dim3(C::THREADS), C::LDS, s, p);
     NRV_CHECK_LAUNCH();
     return 0;
 }
 
-int device_cus();
-
 template <typename C, int EPI, bool OUT_F32, bool AUX_F32>
-int launch_nt8_cfg(GemmNTParams p, hipStream_t s) {
+int launch_nt8_cfg(GemmNTParams p, const NtPlan& pl, hipStream_t s) {
     constexpr int LDS = nt8_lds_bytes<C>();
     static int attr = set_lds(gemm_nt8_kernel<C, EPI, OUT_F32, AUX_F32>, LDS);
     if (attr != 0) return attr;
-    const int tiles_m = (int)nrv_cdiv(p.e.M, C::TBM), tiles_n = (int)nrv_cdiv(p.e.N, C::TBN);
-    p.tiles_n = tiles_n;
+    if (pl.tbm != C::TBM || pl.tbn != C::TBN || !pl.phased) return NRV_ERR_SHAPE;     // plan / instantiation mismatch: never launched
+    p.tiles_n = pl.tiles_n;
     p.gn = 4;
-    p.ntiles = tiles_m * tiles_n;
-    // persistent: one workgroup per CU walks the tiles b, b + grid, ... (the grid stays a multiple of the 8 XCDs so that a
-    // workgroup's tiles stay on its XCD's share of the tile order)
-    const int cus = device_cus() & ~7;
-    const int grid = NRV_TUNE_NT8_GRID(p.ntiles < cus || cus <= 0 ? p.ntiles : cus, p.ntiles);      // identity in the product (csrc/nrv_dev.hpp)
-    hipLaunchKernelGGL((gemm_nt8_kernel<C, EPI, OUT_F32, AUX_F32>), dim3(grid), dim3(C::THREADS), LDS, s, p);
+    p.ntiles = pl.ntiles;
+    hipLaunchKernelGGL((gemm_nt8_kernel<C, EPI, OUT_F32, AUX_F32>), dim3(pl.grid), dim3(C::THREADS), LDS, s, p);
     NRV_CHECK_LAUNCH();
     return 0;
 }
@@ -1742,34 +1747,59 @@ int nt_tile_choice(int64_t M, int64_t N, int64_t K, bool allow_384n) {
     return best;
 }
 
-template <int EPI, bool OUT_F32, bool AUX_F32>
-int launch_nt(const GemmNTParams& p, hipStream_t s) {
+NtPlan nt_plan(int64_t M, int64_t N, int64_t K, int epi, bool remap) {
+    NtPlan pl{};
     // with the fp32 residual epilogue and a long K the 256 x 256 tile wins although it computes the padding columns
     // (profiles/r04_nt8_384x128_tile_phased.txt: [50432 x 384 x 1536] 91.5 vs 93.6 us with both tiles on the phased kernel)
-    const bool allow_384n = !(EPI == NRV_EPI_BIAS_RESIDUAL && p.K >= 1024);
-    const int tc = NRV_TUNE_NT_TILE(nt_tile_choice(p.e.M, p.e.N, p.K, allow_384n));      // identity in the product (csrc/nrv_dev.hpp)
-    if (EPI == NRV_EPI_BIAS_RESIDUAL && (p.e.out_group > 0 || p.e.aux_row_mod > 0))       // row scatter / operand-row broadcast
-        return launch_nt_cfg<Cfg256, NRV_EPI_BIAS_RESIDUAL, OUT_F32, AUX_F32, true>(p, s);    // one launch per step: 256-row tiles only
-    if (tc == 1384) {
-        if ((p.K & (BK - 1)) == 0 && p.K >= 3 * BK) return launch_nt8_cfg<Cfg384n, EPI, OUT_F32, AUX_F32>(p, s);
-        return launch_nt_cfg<Cfg384n, EPI, OUT_F32, AUX_F32, false>(p, s);
-    }
+    const bool allow_384n = !(epi == NRV_EPI_BIAS_RESIDUAL && K >= 1024);
+    const int tc = NRV_TUNE_NT_TILE(nt_tile_choice(M, N, K, allow_384n));      // identity in the product (csrc/nrv_dev.hpp)
+    pl.remap = epi == NRV_EPI_BIAS_RESIDUAL && remap;     // row scatter / operand-row broadcast: one launch per step, 256-row tiles only
+    pl.tile = pl.remap ? 256 : tc;
+    pl.tbm = pl.tile == 1384 ? 384 : pl.tile;
+    pl.tbn = pl.tile == 1384 ? 128 : 256;
     // phased main loop: whole K-steps only, and at least three of them (its prologue issues 1.5 K-steps, its tail peels two)
-    if ((p.K & (BK - 1)) == 0 && p.K >= 3 * BK) {
-        if (tc == 320) return launch_nt8_cfg<Cfg320, EPI, OUT_F32, AUX_F32>(p, s);
-        if (tc == 192) return launch_nt8_cfg<Cfg192, EPI, OUT_F32, AUX_F32>(p, s);
-        if (tc == 128) return launch_nt8_cfg<Cfg128, EPI, OUT_F32, AUX_F32>(p, s);
-        return launch_nt8_cfg<Cfg256, EPI, OUT_F32, AUX_F32>(p, s);
+    pl.phased = !pl.remap && (K & (BK - 1)) == 0 && K >= 3 * BK;
+    pl.tiles_m = (int)nrv_cdiv(M, pl.tbm);
+    pl.tiles_n = (int)nrv_cdiv(N, pl.tbn);
+    pl.ntiles = pl.tiles_m * pl.tiles_n;
+    pl.grid = pl.ntiles;
+    if (pl.phased) {
+        // persistent: one workgroup per CU walks the tiles b, b + grid, ... (the grid stays a multiple of the 8 XCDs so that a
+        // workgroup's tiles stay on its XCD's share of the tile order)
+        const int cus = device_cus() & ~7;
+        pl.grid = NRV_TUNE_NT8_GRID(pl.ntiles < cus || cus <= 0 ? pl.ntiles : cus, pl.ntiles);      // identity in the product (csrc/nrv_dev.hpp)
     }
-    if (tc == 320) return launch_nt_cfg<Cfg320, EPI, OUT_F32, AUX_F32, false>(p, s);
-    if (tc == 192) return launch_nt_cfg<Cfg192, EPI, OUT_F32, AUX_F32, false>(p, s);
-    if (tc == 128) return launch_nt_cfg<Cfg128, EPI, OUT_F32, AUX_F32, false>(p, s);
-    return launch_nt_cfg<Cfg256, EPI, OUT_F32, AUX_F32, false>(p, s);
+    return pl;
 }
 
-// TN launch plan: 256 x 256 tiles and the number of token splits that fills the CUs
-struct TnPlan { int tiles_m, tiles_n, splits; };
-TnPlan tn_plan(int64_t M, int64_t N, int64_t T) {
+template <int EPI, bool OUT_F32, bool AUX_F32>
+int launch_nt(const GemmNTParams& p, hipStream_t s) {
+    const NtPlan pl = nt_plan(p.e.M, p.e.N, p.K, EPI, p.e.out_group > 0 || p.e.aux_row_mod > 0);
+    if (pl.remap)
+        return launch_nt_cfg<Cfg256, NRV_EPI_BIAS_RESIDUAL, OUT_F32, AUX_F32, true>(p, pl, s);
+    if (pl.phased) {
+        if (pl.tile == 1384) return launch_nt8_cfg<Cfg384n, EPI, OUT_F32, AUX_F32>(p, pl, s);
+        if (pl.tile == 320) return launch_nt8_cfg<Cfg320, EPI, OUT_F32, AUX_F32>(p, pl, s);
+        if (pl.tile == 192) return launch_nt8_cfg<Cfg192, EPI, OUT_F32, AUX_F32>(p, pl, s);
+        if (pl.tile == 128) return launch_nt8_cfg<Cfg128, EPI, OUT_F32, AUX_F32>(p, pl, s);
+        return launch_nt8_cfg<Cfg256, EPI, OUT_F32, AUX_F32>(p, pl, s);
+    }
+    if (pl.tile == 1384) return launch_nt_cfg<Cfg384n, EPI, OUT_F32, AUX_F32, false>(p, pl, s);
+    if (pl.tile == 320) return launch_nt_cfg<Cfg320, EPI, OUT_F32, AUX_F32, false>(p, pl, s);
+    if (pl.tile == 192) return launch_nt_cfg<Cfg192, EPI, OUT_F32, AUX_F32, false>(p, pl, s);
+    if (pl.tile == 128) return launch_nt_cfg<Cfg128, EPI, OUT_F32, AUX_F32, false>(p, pl, s);
+    return launch_nt_cfg<Cfg256, EPI, OUT_F32, AUX_F32, false>(p, pl, s);
+}
+
+// TN launch plan: 256 x 256 tiles, the number of token splits that fills the CUs, the K-tiles of a split, which kernel, and where the
+// kernel stores.  The launch (nrv_gemm_tn_bf16), the workspace size and the read-only query (nrv_gemm_tn_plan) all go through it.
+struct TnPlan {
+    int tiles_m, tiles_n, splits;
+    int kt_q, kt_r;         // K-tiles (of 64 token rows) per split: kt_q, the first kt_r splits one more
+    bool phased;            // gemm_tn8_kernel: no row remap of A, at least three K-steps in every split
+    bool direct;            // one split and beta == 0: the kernel stores into the caller's C, no slabs
+};
+TnPlan tn_plan(int64_t M, int64_t N, int64_t T, bool a_group = false, float beta = 0.f) {
     TnPlan pl;
     pl.tiles_m = (int)nrv_cdiv(M, 256);
     pl.tiles_n = (int)nrv_cdiv(N, 256);
@@ -1779,6 +1809,10 @@ TnPlan tn_plan(int64_t M, int64_t N, int64_t T) {
     if (s > kt) s = kt;
     if (s < 1) s = 1;
     pl.splits = (int)s;
+    pl.kt_q = (int)(kt / s);
+    pl.kt_r = (int)(kt % s);
+    pl.phased = !a_group && pl.kt_q >= 3;
+    pl.direct = pl.splits == 1 && beta == 0.f;
     return pl;
 }
 
@@ -1853,6 +1887,31 @@ extern "C" int nrv_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int64
     }
 }
 
+extern "C" int nrv_gemm_nt_plan(int64_t M, int64_t N, int64_t K, int epilogue_id, int remap, nrv_nt_plan* plan) {
+    if (!plan) return NRV_ERR_NULL;
+    if (M <= 0 || N <= 0 || K <= 0) return NRV_ERR_SHAPE;
+    if (M > 0x7fffff00ll || N > 0x7fffff00ll || K > 0x7fffff00ll || (K & 7) || (N & 7)) return NRV_ERR_SHAPE;
+    if (epilogue_id < NRV_EPI_NONE || epilogue_id > NRV_EPI_DGELU_Q8) return NRV_ERR_EPILOGUE;
+    if (remap && epilogue_id != NRV_EPI_BIAS_RESIDUAL) return NRV_ERR_EPILOGUE;
+    if (epi_q8(epilogue_id) && (N & 63)) return NRV_ERR_SHAPE;
+    const NtPlan pl = nt_plan(M, N, K, epilogue_id, remap != 0);
+    plan->tile_m = pl.tbm; plan->tile_n = pl.tbn; plan->phased = pl.phased ? 1 : 0;
+    plan->tiles = pl.ntiles; plan->grid = pl.grid;
+    return 0;
+}
+
+extern "C" int nrv_gemm_tn_plan(int64_t M, int64_t N, int64_t T, int a_group, float beta, int dbias, nrv_tn_plan* plan) {
+    if (!plan) return NRV_ERR_NULL;
+    if (M <= 0 || N <= 0 || T <= 0) return NRV_ERR_SHAPE;
+    if (M > 0x7fffff00ll || N > 0x7fffff00ll || T > 0x7fffff00ll || (M & 7) || (N & 7)) return NRV_ERR_SHAPE;
+    if (beta != 0.f && beta != 1.f) return NRV_ERR_SHAPE;
+    const TnPlan pl = tn_plan(M, N, T, a_group != 0, beta);
+    plan->tiles = pl.tiles_m * pl.tiles_n; plan->splits = pl.splits; plan->kt_q = pl.kt_q; plan->kt_r = pl.kt_r;
+    plan->phased = pl.phased ? 1 : 0; plan->direct = pl.direct ? 1 : 0;
+    plan->reduce = (!pl.direct || dbias) ? 1 : 0;
+    return 0;
+}
+
 extern "C" int nrv_set_reserved_cus(int n) {
     if (n < 0 || physical_cus() - n < 8) return NRV_ERR_SHAPE;
     return g_reserved_cus.exchange(n, std::memory_order_relaxed);
@@ -1876,15 +1935,13 @@ extern "C" int nrv_gemm_tn_bf16(const void* A, int64_t lda, const void* B, int64
     if (!nrv_aligned16(A) || !nrv_aligned16(B) || !nrv_aligned16(C)) return NRV_ERR_ALIGN;
     if (beta != 0.f && beta != 1.f) return NRV_ERR_SHAPE;
     if (a_group < 0 || (a_group > 0 && a_group_stride < a_group)) return NRV_ERR_SHAPE;
-    const TnPlan pl = tn_plan(M, N, T);
-    const int splits = pl.splits;
-    const int64_t kt_total = nrv_cdiv(T, BK);
-    const int kt_q = (int)(kt_total / splits), kt_r = (int)(kt_total % splits);
+    const TnPlan pl = tn_plan(M, N, T, a_group > 0, beta);
+    const int splits = pl.splits, kt_q = pl.kt_q, kt_r = pl.kt_r;
     const int kt_per_split = kt_q + (kt_r ? 1 : 0);
     // per-workgroup operand windows must stay below 2 GiB of byte offset
     const int64_t a_rows = a_group > 0 ? (int64_t)kt_per_split * BK * a_group_stride / a_group + a_group_stride : (int64_t)kt_per_split * BK;
     if (a_rows * lda * 2 >= 0x7fffffffll || (int64_t)kt_per_split * BK * ldb * 2 >= 0x7fffffffll) return NRV_ERR_SHAPE;
-    const bool direct = splits == 1 && beta == 0.f;
+    const bool direct = pl.direct;
     const size_t slab_bytes = direct ? 0 : (size_t)splits * (size_t)M * (size_t)N * 4;
     const size_t need = slab_bytes + (dbias ? (size_t)splits * (size_t)M * 4 : 0);
     if (need > 0 && (!workspace || workspace_bytes < need)) return NRV_ERR_WORKSPACE;
@@ -1907,7 +1964,7 @@ extern "C" int nrv_gemm_tn_bf16(const void* A, int64_t lda, const void* B, int64
     p.bias_ws = dbias ? reinterpret_cast<float*>(static_cast<char*>(workspace) + slab_bytes) : nullptr;
 
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (a_group == 0 && kt_q >= 3) {          // phased K loop: no row remap, at least three K-steps in every split
+    if (pl.phased) {                          // phased K loop: no row remap, at least three K-steps in every split
         static int attr = set_lds(gemm_tn8_kernel<TnCfg256>, TnCfg256::LDS);
         if (attr != 0) return attr;
         hipLaunchKernelGGL(gemm_tn8_kernel<TnCfg256>, dim3(p.tiles_mn * splits), dim3(GEMM_THREADS), TnCfg256::LDS, s, p);

@@ -71,6 +71,24 @@ def set_reserved_cus(n: int) -> int:
     return prev
 
 
+def gemm_nt_plan(M: int, N: int, K: int, epilogue: int = EPI_NONE, remap: bool = False) -> dict:
+    """What `gemm_nt` would launch for this shape under the current CU reservation (include/nrv.h nrv_gemm_nt_plan): tile rows
+    and columns, phased or plain kernel, tiles and workgroups.  Read-only; needs no GPU."""
+    pl = _lib.NtPlan()
+    check(_lib.load().nrv_gemm_nt_plan(int(M), int(N), int(K), int(epilogue), int(bool(remap)), ctypes.addressof(pl)),
+          "nrv_gemm_nt_plan")
+    return {"tile_m": pl.tile_m, "tile_n": pl.tile_n, "phased": bool(pl.phased), "tiles": pl.tiles, "grid": pl.grid}
+
+
+def gemm_tn_plan(M: int, N: int, T: int, a_group: bool = False, beta: float = 0.0, dbias: bool = False) -> dict:
+    """What `gemm_tn` would launch (include/nrv.h nrv_gemm_tn_plan): splits, K-tiles per split, kernel, direct or slabs."""
+    pl = _lib.TnPlan()
+    check(_lib.load().nrv_gemm_tn_plan(int(M), int(N), int(T), int(bool(a_group)), float(beta), int(bool(dbias)),
+                                       ctypes.addressof(pl)), "nrv_gemm_tn_plan")
+    return {"tiles": pl.tiles, "splits": pl.splits, "kt_q": pl.kt_q, "kt_r": pl.kt_r, "phased": bool(pl.phased),
+            "direct": bool(pl.direct), "reduce": bool(pl.reduce)}
+
+
 # ----------------------------------------------------------------------------------------------
 # optional per-launch timing (bench.py's roofline leg): HIP events on the stream the kernel runs on
 # ----------------------------------------------------------------------------------------------

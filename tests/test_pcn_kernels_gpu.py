@@ -181,3 +181,32 @@ def test_bad_shapes_are_refused():
     assert lib.nrv_ls_add_f32(fp, fp, fp, fp, ctypes.c_float(0.5), fp, 10, 3, 8, None) == -2                           # rows % per
     assert lib.nrv_ls_add_f32(fp, fp, fp, None, ctypes.c_float(1.0), fp, 10, 1, 6, None) == -2                         # C % 4
     assert lib.nrv_dgelu_rows(fp, p, _lib.NRV_U8, p, 4, 32, None) == -2                                                # q8: C % 64
+    # refusals that return before any launch, each with real, correctly sized buffers
+    u8 = lambda n: torch.zeros(max(int(n), 16), dtype=torch.uint8, device=dev)
+    a, g = torch.zeros(5, 8, dtype=torch.bfloat16, device=dev), torch.zeros(4, 8, dtype=torch.bfloat16, device=dev)
+    w, c8, c4 = torch.zeros(8, 9, device=dev), torch.zeros(8, device=dev), torch.zeros(4, 4, device=dev)
+    need = lib.nrv_dwconv3x3_bwd_workspace(1, 2, 2, 8)
+    ws = u8(need)
+    dwb = lambda gs, gdt, nbytes: lib.nrv_dwconv3x3_bwd(a.data_ptr(), w.data_ptr(), c8.data_ptr(), g.data_ptr(), c8.data_ptr(), c8.data_ptr(), gs, gdt,
+                                                        g.data_ptr(), w.data_ptr(), c8.data_ptr(), ws.data_ptr(), nbytes, 1, 2, 2, 8, None)
+    assert need == 4 * 8 * 4 + 8 * 10 * 4 and dwb(None, _lib.NRV_BF16, need - 1) == -4            # workspace one byte short
+    assert dwb(g.data_ptr(), _lib.NRV_F32, need) == -3                                             # stream dtype
+    assert dwb(a.data_ptr() + 2, _lib.NRV_BF16, need) == -5                                        # stream pointer off by one bf16
+    assert lib.nrv_dwconv3x3_fwd(a.data_ptr() + 2, w.data_ptr(), c8.data_ptr(), g.data_ptr(), c8.data_ptr(), 1, 2, 2, 8, None) == -5
+    assert lib.nrv_dgelu_rows(fp, g.data_ptr(), _lib.NRV_F32, p, 4, 8, None) == -3
+    assert lib.nrv_dgelu_rows(fp, g.data_ptr(), _lib.NRV_BF16, a.data_ptr() + 2, 4, 8, None) == -5
+    need = lib.nrv_se_bwd_workspace(1, 8, 2)
+    se = torch.zeros(2, 8, device=dev)
+    assert need == (2 * 8 + 2) * 4 and lib.nrv_se_bwd(g.data_ptr(), g.data_ptr(), c8.data_ptr(), 1, c8.data_ptr(), c8.data_ptr(), se.data_ptr(),
+                                                      se.data_ptr(), c8.data_ptr(), se.data_ptr(), c8.data_ptr(), se.data_ptr(), c8.data_ptr(),
+                                                      u8(need).data_ptr(), need - 1, 1, 8, 2, None) == -4
+    need = lib.nrv_ls_bwd_workspace(4, 4)
+    assert need == 16 and lib.nrv_ls_bwd(c4.data_ptr(), c4.data_ptr(), c8.data_ptr(), None, ctypes.c_float(1.0), g.data_ptr(), c8.data_ptr(),
+                                         u8(need).data_ptr(), need - 1, 4, 1, 4, None) == -4
+    assert lib.nrv_cls_attn_fwd(p, 64, p, 64, None, 64, p, 64, p, 64, p, 64, fp, 2, 1, 4, 64, s, None) == -1           # kp NULL, Np > 0
+    assert lib.nrv_cls_attn_bwd(p, 64, p, 64, p, 64, p, 64, None, 64, p, 64, fp, p, p, p, p, p, 2, 1, 4, 64, s, None) == -1
+    assert lib.nrv_cls_attn_fwd(p, 68, p, 64, p, 64, p, 64, p, 64, p, 64, fp, 2, 1, 4, 64, s, None) == -2              # ld % 8
+    assert lib.nrv_cls_attn_bwd(p, 64, p, 64, p, 64, p, 64, p, 64, p, 68, fp, p, p, p, p, p, 2, 1, 4, 64, s, None) == -2
+    big = torch.zeros(65536, 8, dtype=torch.bfloat16, device=dev)                                                       # B > 65535
+    bigsq = torch.zeros(65536, 8, device=dev)
+    assert lib.nrv_dwconv3x3_fwd(big.data_ptr(), w.data_ptr(), c8.data_ptr(), big.data_ptr(), bigsq.data_ptr(), 65536, 1, 1, 8, None) == -2

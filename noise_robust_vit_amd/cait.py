@@ -38,10 +38,8 @@ from torch import nn
 
 from . import encoder as E
 from . import kernels as K
-from ._lib import EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_Q8, EPI_DGELU, EPI_DGELU_Q8, EPI_NONE, PATCH_P1P2C
+from ._lib import EPI_NONE, PATCH_P1P2C
 from .encoder import WEIGHTS
-from .patch_convnet import _dx_sum, _wgrad
-from .swin import LayerNormFn, _require_cuda
 
 Tensor = torch.Tensor
 
@@ -175,47 +173,30 @@ class LayerFn(torch.autograd.Function):
             stats = None
         o = torch.empty(B * n, inner, dtype=torch.bfloat16, device=dev)
         K.bgemm((A, 0), mat, (kv, inner), skv, (o, 0), sq, B, H, n, dh, Nk, 1.0)
-        wob, _ = WEIGHTS.get(wo, True)
-        y1 = K.gemm_nt(o, wob, out_dtype=torch.float32, epilogue=EPI_BIAS, bias=bo.detach())
+        y1 = E.linear(o, wo, bo, torch.float32)
         x1 = K.ls_add(x, y1, sa.detach().reshape(D))
-        h, m2, r2 = K.layernorm_fwd(x1, n2w, n2b, eps2)
-        wf1b, _ = WEIGHTS.get(wf1, True)
-        rows, F = x.shape[0], wf1.shape[0]
-        if F % 64 == 0:
-            gd = torch.empty((rows + 1) // 2 * 2, F, dtype=torch.uint8, device=dev)
-            f1 = K.gemm_nt(h, wf1b, out_dtype=torch.bfloat16, epilogue=EPI_BIAS_GELU_Q8, bias=bf1.detach(), aux_out=gd)
-        else:
-            gd = torch.empty(rows, F, dtype=torch.bfloat16, device=dev)
-            f1 = K.gemm_nt(h, wf1b, out_dtype=torch.bfloat16, epilogue=EPI_BIAS_GELU, bias=bf1.detach(), aux_out=gd)
-        wf2b, _ = WEIGHTS.get(wf2, True)
-        y2 = K.gemm_nt(f1, wf2b, out_dtype=torch.float32, epilogue=EPI_BIAS, bias=bf2.detach())
-        x2 = K.ls_add(x1, y2, sf.detach().reshape(D))
+        q8 = wf1.shape[0] % 64 == 0                  # mlp_dim: the byte stream needs whole 64-column tiles
+        x2, mlp = E.ls_mlp_half_fwd(x1, eps2, n2w, n2b, wf1, bf1, wf2, bf2, sf.detach().reshape(D), q8)
         ctx.meta = meta
-        ctx.saved = (x, c16, xn, mean, rstd, q, kv, S, P, A, stats, o, y1, x1, h, m2, r2, gd, f1, y2)
+        ctx.saved = (x, c16, xn, mean, rstd, q, kv, S, P, A, stats, o, y1, mlp)
         ctx.params = (n1w, wq, wkv, w1, w2, wo, sa, n2w, wf1, wf2, sf)
         return x2
 
     @staticmethod
     def backward(ctx, dx2):
         B, n, N, H, dh, scale, robust, _, _ = ctx.meta
-        x, c16, xn, mean, rstd, q, kv, S, P, A, stats, o, y1, x1, h, m2, r2, gd, f1, y2 = ctx.saved
+        x, c16, xn, mean, rstd, q, kv, S, P, A, stats, o, y1, mlp = ctx.saved
         n1w, wq, wkv, w1, w2, wo, sa, n2w, wf1, wf2, sf = ctx.params
         ctx.saved = None
         inner, Nk, D = H * dh, n + N, x.shape[1]
         dev = x.device
         dx2 = dx2.to(torch.float32).contiguous()
         # feed-forward half
-        dz2, dsf = K.ls_bwd(dx2, y2, sf.detach().reshape(D))
-        dwf2, dbf2 = K.gemm_tn(dz2, f1, want_dbias=True)
-        _, wf2t = WEIGHTS.get(wf2, True)
-        dh16 = K.gemm_nt(dz2, wf2t, out_dtype=torch.bfloat16, epilogue=EPI_DGELU_Q8 if gd.dtype == torch.uint8 else EPI_DGELU, aux=gd)
-        dwf1, dbf1 = K.gemm_tn(dh16, h, want_dbias=True)
-        dhn = _dx_sum([(dh16, wf1)], torch.bfloat16)
-        dx1, _, dn2w, dn2b = K.layernorm_bwd(dhn, x1, n2w.detach(), m2, r2, dres=dx2)
+        dx1, (dsf, dn2w, dn2b, dwf1, dbf1, dwf2, dbf2) = E.ls_mlp_half_bwd(dx2, mlp, n2w, wf1, wf2, sf.detach().reshape(D))
         # attention half
         dz1, dsa = K.ls_bwd(dx1, y1, sa.detach().reshape(D))
         dwo, dbo = K.gemm_tn(dz1, o, want_dbias=True)
-        do = _dx_sum([(dz1, wo)], torch.bfloat16)
+        do = E.dx_sum([(dz1, wo)], torch.bfloat16)
         sq, skv, skvT, mat, matT = _strides(n, Nk, H, dh)
         dq = torch.empty(B * n, inner, dtype=torch.bfloat16, device=dev)
         dkv = torch.empty(B, Nk, 2 * inner, dtype=torch.bfloat16, device=dev)
@@ -244,16 +225,16 @@ class LayerFn(torch.autograd.Function):
         if N:
             dkx = dkv[:, :n].reshape(B * n, 2 * inner).contiguous()
             dkc = dkv[:, n:].reshape(B * N, 2 * inner).contiguous()
-            dwkv, _ = _wgrad([dkx, dkc], [xn, c16], False)
+            dwkv, _ = E.wgrad([dkx, dkc], [xn, c16], False)
             _, wkvt = WEIGHTS.get(wkv, True)
             dctx = K.gemm_nt(dkc, wkvt, out_dtype=torch.float32)
         else:
             dkx = dkv.view(B * n, 2 * inner)
             dwkv = K.gemm_tn(dkx, xn)
-        dxn = _dx_sum([(dq, wq), (dkx, wkv)], torch.bfloat16)
+        dxn = E.dx_sum([(dq, wq), (dkx, wkv)], torch.bfloat16)
         dx, _, dn1w, dn1b = K.layernorm_bwd(dxn, x, n1w.detach(), mean, rstd, dres=dx1)
         return (dx, dctx, None, None, dn1w, dn1b, dwq.reshape(wq.shape), dwkv.reshape(wkv.shape), dw1, dw2, dwo.reshape(wo.shape),
-                dbo, dsa.reshape(sa.shape), dn2w, dn2b, dwf1.reshape(wf1.shape), dbf1, dwf2.reshape(wf2.shape), dbf2,
+                dbo, dsa.reshape(sa.shape), dn2w, dn2b, dwf1, dbf1, dwf2, dbf2,
                 dsf.reshape(sf.shape))
 
 
@@ -274,9 +255,9 @@ class Transformer(nn.Module):
             ]))
 
     def _check_forward(self, x, context=None) -> None:
-        _require_cuda(x)
+        E.require_cuda(x)
         if context is not None:
-            _require_cuda(context)
+            E.require_cuda(context)
         if E._RECORDING is not None:
             raise NotImplementedError("attention-map recording is not implemented for CaiT")
         if self.training and self.dropout > 0:
@@ -349,7 +330,7 @@ class CaiT(nn.Module):
         return max(self.patch_transformer.layer_dropout, self.cls_transformer.layer_dropout)
 
     def _check_forward(self, img) -> None:
-        _require_cuda(img)
+        E.require_cuda(img)
         if E._RECORDING is not None:
             raise NotImplementedError("attention-map recording is not implemented for CaiT")
         if self.training and (self.dropout.p > 0 or self.patch_transformer.dropout > 0 or self.cls_transformer.dropout > 0):
@@ -376,4 +357,4 @@ class CaiT(nn.Module):
         cls = self.cls_token.expand(B, 1, D).reshape(B, D).contiguous()
         cls = self.cls_transformer.run(cls, B, 1, x, n)
         norm, head = self.mlp_head[0], self.mlp_head[1]
-        return head(LayerNormFn.apply(cls, norm.weight, norm.bias, float(norm.eps)))
+        return head(E.LayerNormFn.apply(cls, norm.weight, norm.bias, float(norm.eps)))

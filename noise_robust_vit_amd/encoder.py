@@ -121,6 +121,96 @@ class WeightCache:
 WEIGHTS = WeightCache()
 
 
+# ----------------------------------------------------------------------------------------------
+# host helpers shared by the model ports (Swin, LeViT, PatchConvNet, CaiT, T2T-ViT): a port imports them from here, never
+# from another port
+# ----------------------------------------------------------------------------------------------
+def require_cuda(x: Tensor) -> None:
+    if not x.is_cuda:
+        raise NrvError("noise_robust_vit_amd runs on the MI355X (HIP) device only: move the module and its input to 'cuda'.  "
+                       "There is deliberately no CPU fallback on this path.")
+
+
+_INDEX_CACHE = {}
+
+
+def cached(kind: str, fn, *args, device) -> Tensor:
+    """fn(*args) (an index tensor built by host arithmetic) on `device`, built once per (kind, args, device)."""
+    key = (kind, args, str(device))
+    t = _INDEX_CACHE.get(key)
+    if t is None:
+        if len(_INDEX_CACHE) > 256:
+            _INDEX_CACHE.clear()
+        t = fn(*args).to(device)
+        _INDEX_CACHE[key] = t
+    return t
+
+
+def rows_bf16(src: Tensor, index: Tensor) -> Tensor:
+    """bf16 row gather through the fp32 row kernel: a row of C bf16 is C / 2 fp32 words (C % 8 == 0)."""
+    return K.gather_rows(src.view(torch.float32), index).view(torch.bfloat16)
+
+
+def scatter_bf16(src: Tensor, index: Tensor, rows: int) -> Tensor:
+    return K.scatter_rows(src.view(torch.float32), index, rows).view(torch.bfloat16)
+
+
+def conv_images(w: Tensor, KP: int):
+    """bf16 images of a Conv2d weight [Co, C, ks, ks] in the unfold's (ky, kx, c) feature order, padded to KP columns."""
+    Co = w.shape[0]
+    w2 = w.detach().permute(0, 2, 3, 1).reshape(Co, -1)
+    if w2.shape[1] != KP:
+        w2 = torch.nn.functional.pad(w2, (0, KP - w2.shape[1]))
+    return K.cast_transpose(w2.contiguous(), need_t=True)
+
+
+def linear(x16: Tensor, w: Tensor, b: Optional[Tensor], out_dtype=torch.bfloat16) -> Tensor:
+    wb, _ = WEIGHTS.get(w, True)
+    if b is None:
+        return K.gemm_nt(x16, wb, out_dtype=out_dtype, epilogue=EPI_NONE)
+    return K.gemm_nt(x16, wb, out_dtype=out_dtype, epilogue=EPI_BIAS, bias=b.detach())
+
+
+def wgrad(dys, xs, want_bias: bool):
+    """sum_i dys[i]^T xs[i] (and the bias gradient): the class rows' and the patch rows' contributions to one weight."""
+    dw, db = K.gemm_tn(dys[0], xs[0], want_dbias=True) if want_bias else (K.gemm_tn(dys[0], xs[0]), None)
+    for dy, x in zip(dys[1:], xs[1:]):
+        if want_bias:
+            K.gemm_tn(dy, x, out=dw, beta=1.0, dbias=db, dbias_beta=1.0)
+        else:
+            K.gemm_tn(dy, x, out=dw, beta=1.0)
+    return dw, db
+
+
+def dx_sum(pairs, out_dtype):
+    """sum_i d_i W_i: the input gradient of several Linears that read the same rows (EPI_BIAS_RESIDUAL chains the sum)."""
+    acc = None
+    for i, (d16, w) in enumerate(pairs):
+        _, wt = WEIGHTS.get(w, True)
+        dt = out_dtype if i == len(pairs) - 1 else torch.float32
+        acc = K.gemm_nt(d16, wt, out_dtype=dt) if acc is None else K.gemm_nt(d16, wt, out_dtype=dt, epilogue=EPI_BIAS_RESIDUAL, aux=acc)
+    return acc
+
+
+class LayerNormFn(torch.autograd.Function):
+    """nn.LayerNorm on fp32 rows [R, D] through the HIP kernels; the bf16 result is returned widened to fp32 (the stream)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, eps: float):
+        x = x.detach().contiguous()
+        y, mean, rstd = K.layernorm_fwd(x, w, b, eps)
+        ctx.save_for_backward(x, mean, rstd)
+        ctx.w = w
+        return y.to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, rstd = ctx.saved_tensors
+        d16 = K.cast_bf16(dy.to(torch.float32).contiguous())
+        dx, _, dg, db = K.layernorm_bwd(d16, x, ctx.w, mean, rstd, want_f32=True)
+        return dx, dg, db, None
+
+
 @dataclass
 class BlockMeta:
     heads: int
@@ -480,18 +570,31 @@ def attn_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, B: int,
 GELU_STREAM_U8 = True        # False: the bf16 gelu' stream of rounds 1 - 3 (A/B, tests)
 
 
+def fc1_gelu(xn: Tensor, w1_b: Tensor, b1: Tensor, q8: bool, save: bool = True):
+    """h = gelu(xn W1^T + b1) on the staged bf16 image `w1_b`.  Returns (h, u): u = gelu'(pre-activation) for
+    `dgelu_bwd`, or None with save=False (no gradient will be asked for).  `q8` is the caller's rule and needs
+    W1 rows % 64 == 0: one byte per element in row pairs (include/nrv.h NRV_EPI_BIAS_GELU_Q8), else bf16."""
+    T, F = xn.shape[0], w1_b.shape[0]
+    rows, dtype = ((T + 1) // 2 * 2, torch.uint8) if q8 else (T, torch.bfloat16)
+    u = torch.empty(rows, F, dtype=dtype, device=xn.device) if save else None
+    h = K.gemm_nt(xn, w1_b, out_dtype=torch.bfloat16, epilogue=EPI_BIAS_GELU_Q8 if q8 else EPI_BIAS_GELU, bias=b1, aux_out=u)
+    return h, u
+
+
+def dgelu_bwd(dy16: Tensor, w2_t: Tensor, u: Tensor) -> Tensor:
+    """du = (dy W2) o gelu', the stream as `fc1_gelu` saved it (bytes or bf16)."""
+    return K.gemm_nt(dy16, w2_t, out_dtype=torch.bfloat16, epilogue=EPI_DGELU_Q8 if u.dtype == torch.uint8 else EPI_DGELU, aux=u)
+
+
 def mlp_half_fwd(x: Tensor, meta: BlockMeta, ln_w, ln_b, w1, b1, w2, b2, residual: bool, save: bool = True, drop=None):
     """`save=False` (no gradient will be asked for): the fc1 epilogue skips the gelu'(u) output -- a 310 MB store stream per
     layer on ViT-B/16 at batch 256."""
     xn, mean, rstd = K.layernorm_fwd(x, ln_w, ln_b, meta.eps)
     w1_b, _ = WEIGHTS.get(w1, True)
     w2_b, _ = WEIGHTS.get(w2, True)
-    T = x.shape[0]
-    # gelu'(pre-activation) for the backward: one byte per element (include/nrv.h NRV_EPI_BIAS_GELU_Q8) unless a dropout mask is
-    # going to be multiplied into it (a scaled value leaves the byte code's range)
+    # the byte stream, unless a dropout mask is going to be multiplied into it (a scaled value leaves the byte code's range)
     q8 = GELU_STREAM_U8 and drop is None and w1.shape[0] % 64 == 0
-    u = torch.empty((T + 1) // 2 * 2 if q8 else T, w1.shape[0], dtype=torch.uint8 if q8 else torch.bfloat16, device=x.device) if save else None
-    h = K.gemm_nt(xn, w1_b, out_dtype=torch.bfloat16, epilogue=EPI_BIAS_GELU_Q8 if q8 else EPI_BIAS_GELU, bias=b1, aux_out=u)
+    h, u = fc1_gelu(xn, w1_b, b1, q8, save)
     keep2 = None
     if drop is not None:
         # Dropout behind the GELU (vit.py:100) and behind the second Linear (vit.py:101).  The first mask is applied to the saved
@@ -525,7 +628,7 @@ def mlp_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, meta: Bl
     _, w2_t = WEIGHTS.get(w2, True)
     _, w1_t = WEIGHTS.get(w1, True)
     dw2, db2 = _dw_db(meta, dy16, h, w2, b2, None if need is None else need[4:6])
-    du = K.gemm_nt(dy16, w2_t, out_dtype=torch.bfloat16, epilogue=EPI_DGELU_Q8 if u.dtype == torch.uint8 else EPI_DGELU, aux=u)
+    du = dgelu_bwd(dy16, w2_t, u)
     dw1, db1 = _dw_db(meta, du, xn, w1, b1, None if need is None else need[2:4])
     dxn = K.gemm_nt(du, w1_t, out_dtype=torch.bfloat16)
     tg, bg = _grad_target(meta, ln_w)
@@ -536,13 +639,34 @@ def mlp_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, meta: Bl
     return dx32, dx16, [dg, db, dw1, db1, dw2, db2]
 
 
+def ls_mlp_half_fwd(x: Tensor, eps: float, ln_w, ln_b, w1, b1, w2, b2, gamma: Tensor, q8: bool):
+    """The layer-scaled MLP half of CaiT and of PatchConvNet's class-token block: x + gamma * fc2(gelu(fc1(LN x))), x fp32 [R, D],
+    gamma fp32 [D].  The caller decides `q8` (see `fc1_gelu`); no gradient sink.  Returns (y, saved) for `ls_mlp_half_bwd`."""
+    xn, mean, rstd = K.layernorm_fwd(x, ln_w, ln_b, eps)
+    w1_b, _ = WEIGHTS.get(w1, True)
+    h, u = fc1_gelu(xn, w1_b, b1.detach(), q8)
+    yb = linear(h, w2, b2, torch.float32)
+    return K.ls_add(x, yb, gamma), (x, xn, mean, rstd, u, h, yb)
+
+
+def ls_mlp_half_bwd(dy: Tensor, saved, ln_w, w1, w2, gamma: Tensor):
+    """dy fp32 [R, D] -> (dx fp32, [d gamma, d ln_w, d ln_b, d w1, d b1, d w2, d b2])."""
+    x, xn, mean, rstd, u, h, yb = saved
+    dz, dgamma = K.ls_bwd(dy, yb, gamma)
+    dw2, db2 = K.gemm_tn(dz, h, want_dbias=True)
+    _, w2_t = WEIGHTS.get(w2, True)
+    du = dgelu_bwd(dz, w2_t, u)
+    dw1, db1 = K.gemm_tn(du, xn, want_dbias=True)
+    dxn = dx_sum([(du, w1)], torch.bfloat16)
+    dx, _, dg, db = K.layernorm_bwd(dxn, x, ln_w.detach(), mean, rstd, dres=dy)
+    return dx, [dgamma, dg, db, dw1.reshape(w1.shape), db1, dw2.reshape(w2.shape), db2]
+
+
 # ----------------------------------------------------------------------------------------------
 # autograd boundary
 # ----------------------------------------------------------------------------------------------
 def _as_stream(x: Tensor):
-    if not x.is_cuda:
-        raise NrvError("noise_robust_vit_amd runs on the MI355X (HIP) device only: move the module and its input "
-                       "to 'cuda'.  There is deliberately no CPU fallback on this path.")
+    require_cuda(x)
     if x.dim() != 3:
         raise NrvError(f"expected (batch, tokens, dim), got {tuple(x.shape)}")
     B, N, D = x.shape
@@ -784,9 +908,7 @@ class PatchEmbedFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, img, weight, bias, pos, cls_token, patch: int, layout: int, sink):
-        if not img.is_cuda:
-            raise NrvError("noise_robust_vit_amd runs on the MI355X (HIP) device only: move the module and its "
-                           "input to 'cuda'.  There is deliberately no CPU fallback on this path.")
+        require_cuda(img)
         if img.requires_grad:
             raise NrvError("gradient w.r.t. the input image is not part of this hot path")
         Bn, C, H, W = img.shape
@@ -875,9 +997,7 @@ class LinearFn(torch.autograd.Function):
         shp = x.shape
         x2 = x.detach().to(torch.float32).contiguous().reshape(-1, shp[-1])
         xb = K.cast_bf16(x2)
-        wb, _ = WEIGHTS.get(weight, True)
-        y = K.gemm_nt(xb, wb, out_dtype=torch.float32, epilogue=EPI_BIAS if bias is not None else EPI_NONE,
-                      bias=bias.detach() if bias is not None else None)
+        y = linear(xb, weight, bias, torch.float32)
         ctx.save_for_backward(xb)
         ctx.meta = (weight, bias is not None, shp)
         return y.reshape(*shp[:-1], weight.shape[0])

@@ -40,7 +40,6 @@ from . import encoder as E
 from . import kernels as K
 from ._lib import EPI_BIAS_RESIDUAL, NrvError
 from .encoder import WEIGHTS
-from .swin import _cached, _require_cuda, _rows_bf16
 
 Tensor = torch.Tensor
 
@@ -113,15 +112,6 @@ def _dx(d16: Tensor, w: Tensor, dres: Optional[Tensor]) -> Tensor:
 # ----------------------------------------------------------------------------------------------
 # autograd nodes: the stem, and one per block
 # ----------------------------------------------------------------------------------------------
-def _conv_images(w: Tensor, KP: int):
-    """bf16 images of a Conv2d weight [Co, C, ks, ks] in the unfold's (ky, kx, c) feature order, padded to KP columns."""
-    Co = w.shape[0]
-    w2 = w.detach().permute(0, 2, 3, 1).reshape(Co, -1)
-    if w2.shape[1] != KP:
-        w2 = torch.nn.functional.pad(w2, (0, KP - w2.shape[1]))
-    return K.cast_transpose(w2.contiguous(), need_t=True)
-
-
 class StemFn(torch.autograd.Function):
     """b16 (levit.py:166-175): 4 x (Conv2d 3x3 / stride 2 / pad 1 -> BatchNorm2d), Hardswish between them, on NHWC rows.
     Returns the fp32 token stream [B*N, C] (= flatten(2).transpose(1, 2), levit.py:524) and its bf16 image.  The weight images
@@ -135,7 +125,7 @@ class StemFn(torch.autograd.Function):
             c = cbn.c
             Cin, Co = c.in_channels, c.out_channels
             cols = K.conv_unfold(src, B, Cin, H, W, 3, 2, 1, nhwc=li > 0)
-            wb, wt = _conv_images(c.weight, cols.shape[1])
+            wb, wt = E.conv_images(c.weight, cols.shape[1])
             st = _BnState(cbn.bn, K.gemm_nt(cols, wb, out_dtype=torch.float32))
             Ho, Wo = K.conv_out_size(H, 3, 2, 1), K.conv_out_size(W, 3, 2, 1)
             layers.append((cols, wt, st, (Cin, H, W)))
@@ -247,7 +237,7 @@ class SubsampleFn(torch.autograd.Function):
         B, Nq, Nk, H, kd, d = meta.B, meta.Nq, meta.N, a.num_heads, a.key_dim, a.d
         skv = _linear_bn(x16, a.kv)
         _, kv = skv.apply(gkv, bkv)
-        xs16 = _rows_bf16(x16, meta.sub_index)
+        xs16 = E.rows_bf16(x16, meta.sub_index)
         sq = _linear_bn(xs16, a.q[1])
         _, q = sq.apply(gq, bq)
         o, ao, stats = K.bias_attn_fwd(q, kv, kv[:, kd:], kd, kd + d, kd + d, table.detach(), meta.index, B, H, Nq, Nk, kd, d,
@@ -355,7 +345,7 @@ class Conv2d_BN(nn.Sequential):
         _bn_check(self.bn)
 
     def forward(self, x: Tensor) -> Tensor:
-        _require_cuda(x)
+        E.require_cuda(x)
         self._check()
         B, _, H, W = x.shape
         y32, _ = StemFn.apply(x.to(torch.float32), [self], self.c.weight, self.bn.weight, self.bn.bias)
@@ -577,7 +567,7 @@ class LeViT(nn.Module):
         return {x for x in self.state_dict().keys() if "attention_biases" in x}
 
     def forward(self, x: Tensor) -> Tensor:
-        _require_cuda(x)
+        E.require_cuda(x)
         if E._RECORDING is not None:
             raise NotImplementedError("attention-map recording is not implemented for LeViT")
         B, _, Hi, Wi = x.shape
@@ -599,7 +589,7 @@ class LeViT(nn.Module):
                     _bn_check(lbn.bn)
                 Nq = a.resolution_2
                 meta = _Meta(a, B, r * r, Nq, _bias_index(a),
-                             _cached("levit_sub", subsample_index, B, r, a.stride, device=x.device))
+                             E.cached("levit_sub", subsample_index, B, r, a.stride, device=x.device))
                 x32, x16 = SubsampleFn.apply(x32, x16, meta, a.kv.c.weight, a.kv.bn.weight, a.kv.bn.bias,
                                              a.q[1].c.weight, a.q[1].bn.weight, a.q[1].bn.bias, a.attention_biases,
                                              a.proj[1].c.weight, a.proj[1].bn.weight, a.proj[1].bn.bias)

@@ -38,10 +38,8 @@ from torch import nn
 
 from . import encoder as E
 from . import kernels as K
-from ._lib import EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_Q8, EPI_BIAS_RESIDUAL, EPI_DGELU, EPI_NONE
+from ._lib import EPI_BIAS_GELU
 from .encoder import WEIGHTS
-from .levit import _conv_images
-from .swin import LayerNormFn, _require_cuda
 
 Tensor = torch.Tensor
 
@@ -226,7 +224,7 @@ class StemFn(torch.autograd.Function):
         for li, w in enumerate(weights):
             Co = w.shape[0]
             cols = K.conv_unfold(src, B, Cin, H, W, 3, 2, 1, nhwc=li > 0)
-            wb, wt = _conv_images(w, cols.shape[1])
+            wb, wt = E.conv_images(w, cols.shape[1])
             if li < len(weights) - 1:
                 gd = torch.empty(cols.shape[0], Co, dtype=torch.bfloat16, device=img.device)
                 src = K.gemm_nt(cols, wb, out_dtype=torch.bfloat16, epilogue=EPI_BIAS_GELU, bias=_zeros(Co, img.device), aux_out=gd)
@@ -272,17 +270,11 @@ class ConvBlockFn(torch.autograd.Function):
         HW, C = H * W, x.shape[1]
         xn, mean, rstd = K.layernorm_fwd(x, ln_w, ln_b, meta.eps)
         w1b, _ = WEIGHTS.get(w1, True)
-        if C % 64 == 0:
-            u = torch.empty((x.shape[0] + 1) // 2 * 2, C, dtype=torch.uint8, device=x.device)
-            a = K.gemm_nt(xn, w1b, out_dtype=torch.bfloat16, epilogue=EPI_BIAS_GELU_Q8, bias=b1.detach(), aux_out=u)
-        else:
-            u = torch.empty(x.shape[0], C, dtype=torch.bfloat16, device=x.device)
-            a = K.gemm_nt(xn, w1b, out_dtype=torch.bfloat16, epilogue=EPI_BIAS_GELU, bias=b1.detach(), aux_out=u)
+        a, u = E.fc1_gelu(xn, w1b, b1.detach(), q8=C % 64 == 0)
         d, sq = K.dwconv3x3_fwd(a, wdw.detach(), bdw.detach(), B, H, W)
         s, hid = K.se_fwd(sq, HW, wr.detach(), br.detach(), we.detach(), be.detach())
         g = K.se_apply(d, s, HW)
-        w2b, _ = WEIGHTS.get(w2, True)
-        y = K.gemm_nt(g, w2b, out_dtype=torch.float32, epilogue=EPI_BIAS, bias=b2.detach())
+        y = E.linear(g, w2, b2, torch.float32)
         out = K.ls_add(x, y, gamma.detach(), meta.keep, meta.survival)
         ctx.meta = meta
         ctx.saved = (x, xn, mean, rstd, u, a, d, sq, s, hid, g, y)
@@ -310,34 +302,6 @@ class ConvBlockFn(torch.autograd.Function):
                 dgamma)
 
 
-def _linear(x16: Tensor, w: Tensor, b: Optional[Tensor], out_dtype=torch.bfloat16) -> Tensor:
-    wb, _ = WEIGHTS.get(w, True)
-    if b is None:
-        return K.gemm_nt(x16, wb, out_dtype=out_dtype, epilogue=EPI_NONE)
-    return K.gemm_nt(x16, wb, out_dtype=out_dtype, epilogue=EPI_BIAS, bias=b.detach())
-
-
-def _wgrad(dys, xs, want_bias: bool):
-    """sum_i dys[i]^T xs[i] (and the bias gradient): the class rows' and the patch rows' contributions to one weight."""
-    dw, db = K.gemm_tn(dys[0], xs[0], want_dbias=True) if want_bias else (K.gemm_tn(dys[0], xs[0]), None)
-    for dy, x in zip(dys[1:], xs[1:]):
-        if want_bias:
-            K.gemm_tn(dy, x, out=dw, beta=1.0, dbias=db, dbias_beta=1.0)
-        else:
-            K.gemm_tn(dy, x, out=dw, beta=1.0)
-    return dw, db
-
-
-def _dx_sum(pairs, out_dtype):
-    """sum_i d_i W_i: the input gradient of several Linears that read the same rows (EPI_BIAS_RESIDUAL chains the sum)."""
-    acc = None
-    for i, (d16, w) in enumerate(pairs):
-        _, wt = WEIGHTS.get(w, True)
-        dt = out_dtype if i == len(pairs) - 1 else torch.float32
-        acc = K.gemm_nt(d16, wt, out_dtype=dt) if acc is None else K.gemm_nt(d16, wt, out_dtype=dt, epilogue=EPI_BIAS_RESIDUAL, aux=acc)
-    return acc
-
-
 class TokenBlockFn(torch.autograd.Function):
     """Layer_scale_init_Block_only_token (patch_convnet.py:154-218) on the class rows cls [B, C] and the patch stream x [B*N, C]:
         c1 = cls + gamma_1 proj(cls_attn(q(LN1 cls), k / v(LN1 [cls; x])));   c2 = c1 + gamma_2 fc2(gelu(fc1(LN2 c1)))"""
@@ -348,45 +312,35 @@ class TokenBlockFn(torch.autograd.Function):
         B, N, H, dh, scale, eps1, eps2 = meta
         xc, mc, rc = K.layernorm_fwd(cls, n1w, n1b, eps1)
         xp, mp, rp = K.layernorm_fwd(x, n1w, n1b, eps1)
-        q = _linear(xc, wq, bq)
-        kc, kp = _linear(xc, wk, bk), _linear(xp, wk, bk)
-        vc, vp = _linear(xc, wv, bv), _linear(xp, wv, bv)
+        q = E.linear(xc, wq, bq)
+        kc, kp = E.linear(xc, wk, bk), E.linear(xp, wk, bk)
+        vc, vp = E.linear(xc, wv, bv), E.linear(xp, wv, bv)
         o, lse = K.cls_attn_fwd(q, kc, kp, vc, vp, B, H, N, dh, scale)
-        y1 = _linear(o, wp, bp, torch.float32)
+        y1 = E.linear(o, wp, bp, torch.float32)
         c1 = K.ls_add(cls, y1, g1.detach())
-        h, m2, r2 = K.layernorm_fwd(c1, n2w, n2b, eps2)
-        wf1b, _ = WEIGHTS.get(wf1, True)
-        gd = torch.empty(B, wf1.shape[0], dtype=torch.bfloat16, device=x.device)
-        f1 = K.gemm_nt(h, wf1b, out_dtype=torch.bfloat16, epilogue=EPI_BIAS_GELU, bias=bf1.detach(), aux_out=gd)
-        y2 = _linear(f1, wf2, bf2, torch.float32)
-        c2 = K.ls_add(c1, y2, g2.detach())
+        # the stream has B rows, B may be odd: bf16, never the byte stream in row pairs
+        c2, mlp = E.ls_mlp_half_fwd(c1, eps2, n2w, n2b, wf1, bf1, wf2, bf2, g2.detach(), q8=False)
         ctx.meta = meta
-        ctx.saved = (x, cls, xc, mc, rc, xp, mp, rp, q, kc, kp, vc, vp, o, lse, y1, c1, h, m2, r2, gd, f1, y2)
+        ctx.saved = (x, cls, xc, mc, rc, xp, mp, rp, q, kc, kp, vc, vp, o, lse, y1, mlp)
         ctx.params = (n1w, wq, bq, wk, bk, wv, bv, wp, g1, n2w, wf1, wf2, g2)
         return c2
 
     @staticmethod
     def backward(ctx, dc2):
         B, N, H, dh, scale, _, _ = ctx.meta
-        x, cls, xc, mc, rc, xp, mp, rp, q, kc, kp, vc, vp, o, lse, y1, c1, h, m2, r2, gd, f1, y2 = ctx.saved
+        x, cls, xc, mc, rc, xp, mp, rp, q, kc, kp, vc, vp, o, lse, y1, mlp = ctx.saved
         n1w, wq, bq, wk, bk, wv, bv, wp, g1, n2w, wf1, wf2, g2 = ctx.params
         dc2 = dc2.to(torch.float32).contiguous()
-        dz2, dg2 = K.ls_bwd(dc2, y2, g2.detach())
-        dwf2, dbf2 = K.gemm_tn(dz2, f1, want_dbias=True)
-        _, wf2t = WEIGHTS.get(wf2, True)
-        dh16 = K.gemm_nt(dz2, wf2t, out_dtype=torch.bfloat16, epilogue=EPI_DGELU, aux=gd)
-        dwf1, dbf1 = K.gemm_tn(dh16, h, want_dbias=True)
-        dhn = _dx_sum([(dh16, wf1)], torch.bfloat16)
-        dc1, _, dn2w, dn2b = K.layernorm_bwd(dhn, c1, n2w.detach(), m2, r2, dres=dc2)
+        dc1, (dg2, dn2w, dn2b, dwf1, dbf1, dwf2, dbf2) = E.ls_mlp_half_bwd(dc2, mlp, n2w, wf1, wf2, g2.detach())
         dz1, dg1 = K.ls_bwd(dc1, y1, g1.detach())
         dwp, dbp = K.gemm_tn(dz1, o, want_dbias=True)
-        do = _dx_sum([(dz1, wp)], torch.bfloat16)
+        do = E.dx_sum([(dz1, wp)], torch.bfloat16)
         dq, dkc, dkp, dvc, dvp = K.cls_attn_bwd(q, kc, kp, vc, vp, do, lse, B, H, N, dh, scale)
-        dwq, dbq = _wgrad([dq], [xc], bq is not None)
-        dwk, dbk = _wgrad([dkc, dkp], [xc, xp], bk is not None)
-        dwv, dbv = _wgrad([dvc, dvp], [xc, xp], bv is not None)
-        dxc = _dx_sum([(dq, wq), (dkc, wk), (dvc, wv)], torch.bfloat16)
-        dxp = _dx_sum([(dkp, wk), (dvp, wv)], torch.bfloat16)
+        dwq, dbq = E.wgrad([dq], [xc], bq is not None)
+        dwk, dbk = E.wgrad([dkc, dkp], [xc, xp], bk is not None)
+        dwv, dbv = E.wgrad([dvc, dvp], [xc, xp], bv is not None)
+        dxc = E.dx_sum([(dq, wq), (dkc, wk), (dvc, wv)], torch.bfloat16)
+        dxp = E.dx_sum([(dkp, wk), (dvp, wv)], torch.bfloat16)
         dcls, _, dn1w, dn1b = K.layernorm_bwd(dxc, cls, n1w.detach(), mc, rc, dres=dc1)
         dx, _, dn1w, dn1b = K.layernorm_bwd(dxp, x, n1w.detach(), mp, rp, dgamma=dn1w, dbeta=dn1b, accumulate=True)
         return (dx, dcls, None, dn1w, dn1b, dwq, dbq, dwk, dbk, dwv, dbv, dwp, dbp, dg1, dn2w, dn2b, dwf1, dbf1, dwf2, dbf2, dg2)
@@ -482,7 +436,7 @@ class PatchConvnet(nn.Module):
         self.head = nn.Linear(self.embed_dim, num_classes) if num_classes > 0 else nn.Identity()
 
     def _check_forward(self, x: Tensor) -> None:
-        _require_cuda(x)
+        E.require_cuda(x)
         if E._RECORDING is not None:
             raise NotImplementedError("attention-map recording is not implemented for PatchConvNet")
         if any(b.attn.robust for b in self.blocks_token_only):
@@ -518,7 +472,7 @@ class PatchConvnet(nn.Module):
             cls = TokenBlockFn.apply(x32, cls.contiguous(), meta, blk.norm1.weight, blk.norm1.bias, a.q.weight, a.q.bias, a.k.weight,
                                      a.k.bias, a.v.weight, a.v.bias, a.proj.weight, a.proj.bias, blk.gamma_1, blk.norm2.weight,
                                      blk.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, blk.gamma_2)
-        return LayerNormFn.apply(cls.contiguous(), self.norm.weight, self.norm.bias, float(self.norm.eps))
+        return E.LayerNormFn.apply(cls.contiguous(), self.norm.weight, self.norm.bias, float(self.norm.eps))
 
     def forward(self, x: Tensor) -> Tensor:
         return self.head(self.forward_features(x))

@@ -27,7 +27,7 @@ from torch import nn
 
 from . import encoder as E
 from . import kernels as K
-from ._lib import EPI_BIAS, EPI_BIAS_RESIDUAL, EPI_NONE, PATCH_CP1P2, NrvError
+from ._lib import EPI_BIAS, EPI_BIAS_RESIDUAL, EPI_NONE, PATCH_CP1P2
 from .encoder import WEIGHTS, BlockMeta, PatchEmbedFn
 
 Tensor = torch.Tensor
@@ -79,29 +79,6 @@ def merge_index(B: int, H: int, W: int) -> Tensor:
     return torch.where(idx[None] >= 0, idx[None] + b, torch.full_like(idx[None] + b, -1)).reshape(-1).to(torch.int64)
 
 
-_INDEX_CACHE = {}
-
-
-def _cached(kind: str, fn, *args, device) -> Tensor:
-    key = (kind, args, str(device))
-    t = _INDEX_CACHE.get(key)
-    if t is None:
-        if len(_INDEX_CACHE) > 256:
-            _INDEX_CACHE.clear()
-        t = fn(*args).to(device)
-        _INDEX_CACHE[key] = t
-    return t
-
-
-def _rows_bf16(src: Tensor, index: Tensor) -> Tensor:
-    """bf16 row gather through the fp32 row kernel: a row of C bf16 is C / 2 fp32 words (C % 8 == 0)."""
-    return K.gather_rows(src.view(torch.float32), index).view(torch.bfloat16)
-
-
-def _scatter_bf16(src: Tensor, index: Tensor, rows: int) -> Tensor:
-    return K.scatter_rows(src.view(torch.float32), index, rows).view(torch.bfloat16)
-
-
 # ----------------------------------------------------------------------------------------------
 # autograd boundary
 # ----------------------------------------------------------------------------------------------
@@ -115,8 +92,8 @@ class SwinGeom:
         self.shift = (sh, sw)
         self.padded = (self.pH, self.pW) != (H, W)
         if self.padded:
-            self.pad_idx = _cached("pad", pad_index, B, H, W, self.pH, self.pW, device=device)
-            self.real_idx = _cached("real", real_index, B, H, W, self.pH, self.pW, device=device)
+            self.pad_idx = E.cached("pad", pad_index, B, H, W, self.pH, self.pW, device=device)
+            self.real_idx = E.cached("real", real_index, B, H, W, self.pH, self.pW, device=device)
 
     def attn_args(self):
         return (self.B, self.pH, self.pW, self.C, self.heads, self.window, self.shift, self.robust)
@@ -132,13 +109,13 @@ class SwinBlockFn(torch.autograd.Function):
                 ln1_w, ln1_b, wqkv, bqkv, table, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2):
         x = x.detach()
         xn, mean1, rstd1 = K.layernorm_fwd(x, ln1_w, ln1_b, meta.eps)
-        xp = _rows_bf16(xn, geom.pad_idx) if geom.padded else xn
+        xp = E.rows_bf16(xn, geom.pad_idx) if geom.padded else xn
         wqkv_b, _ = WEIGHTS.get(wqkv, True)
         wo_b, _ = WEIGHTS.get(wo, True)
         qkv = K.gemm_nt(xp, wqkv_b, out_dtype=torch.bfloat16, epilogue=EPI_BIAS if bqkv is not None else EPI_NONE,
                         bias=None if bqkv is None else bqkv.detach())
         o, stats = K.window_attn_fwd(qkv, table.detach(), *geom.attn_args())
-        o_real = _rows_bf16(o, geom.real_idx) if geom.padded else o
+        o_real = E.rows_bf16(o, geom.real_idx) if geom.padded else o
         bo_d = None if bo is None else bo.detach()
         if keep1 is not None:
             yb = K.gemm_nt(o_real, wo_b, out_dtype=torch.float32, epilogue=EPI_BIAS if bo is not None else EPI_NONE, bias=bo_d)
@@ -171,33 +148,14 @@ class SwinBlockFn(torch.autograd.Function):
         _, wqkv_t = WEIGHTS.get(wqkv, True)
         do = K.gemm_nt(d16, wo_t, out_dtype=torch.bfloat16)
         if geom.padded:
-            do = _scatter_bf16(do, geom.real_idx, geom.B * geom.pH * geom.pW)
+            do = E.scatter_bf16(do, geom.real_idx, geom.B * geom.pH * geom.pW)
         dqkv, dtable = K.window_attn_bwd(qkv, table.detach(), do, stats, *geom.attn_args())
         dwqkv, dbqkv = E._dw_db(meta, dqkv, xp, wqkv, bqkv)
         dxp = K.gemm_nt(dqkv, wqkv_t, out_dtype=torch.bfloat16)
-        dxn = _rows_bf16(dxp, geom.real_idx) if geom.padded else dxp
+        dxn = E.rows_bf16(dxp, geom.real_idx) if geom.padded else dxp
         dx, _, dg1, db1 = K.layernorm_bwd(dxn, x, ln1_w, mean1, rstd1, dres=d1, want_f32=True)
         grads = E._mask_sink_grads(meta, [dg1, db1, dwqkv, dbqkv, dtable, dwo, dbo] + g_mlp)
         return (dx, None, None, None, None, None, *grads)
-
-
-class LayerNormFn(torch.autograd.Function):
-    """nn.LayerNorm on fp32 rows [R, D] through the HIP kernels; the bf16 result is returned widened to fp32 (the stream)."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, eps: float):
-        x = x.detach().contiguous()
-        y, mean, rstd = K.layernorm_fwd(x, w, b, eps)
-        ctx.save_for_backward(x, mean, rstd)
-        ctx.w = w
-        return y.to(torch.float32)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, mean, rstd = ctx.saved_tensors
-        d16 = K.cast_bf16(dy.to(torch.float32).contiguous())
-        dx, _, dg, db = K.layernorm_bwd(d16, x, ctx.w, mean, rstd, want_f32=True)
-        return dx, dg, db, None
 
 
 class MergeFn(torch.autograd.Function):
@@ -230,12 +188,6 @@ class MergeFn(torch.autograd.Function):
 # ----------------------------------------------------------------------------------------------
 # modules (parameter holders with the reference's names)
 # ----------------------------------------------------------------------------------------------
-def _require_cuda(x: Tensor) -> None:
-    if not x.is_cuda:
-        raise NrvError("noise_robust_vit_amd runs on the MI355X (HIP) device only: move the module and its input to 'cuda'.  "
-                       "There is deliberately no CPU fallback on this path.")
-
-
 def _ln_eps(norm: nn.Module) -> float:
     if not isinstance(norm, nn.LayerNorm) or not norm.elementwise_affine:
         raise NotImplementedError("only nn.LayerNorm with affine parameters is implemented as the Swin norm_layer")
@@ -304,12 +256,12 @@ class PatchMerging(nn.Module):
 
     def run(self, x: Tensor, B: int, H: int, W: int):
         """fp32 stream [B*H*W, C] -> ([B*H2*W2, 2C], H2, W2)."""
-        idx = _cached("merge", merge_index, B, H, W, device=x.device)
+        idx = E.cached("merge", merge_index, B, H, W, device=x.device)
         y = MergeFn.apply(x, idx, _ln_eps(self.norm), self.norm.weight, self.norm.bias, self.reduction.weight)
         return y, (H + 1) // 2, (W + 1) // 2
 
     def forward(self, x: Tensor) -> Tensor:
-        _require_cuda(x)
+        E.require_cuda(x)
         B, H, W, C = x.shape
         y, H2, W2 = self.run(x.to(torch.float32).contiguous().reshape(B * H * W, C), B, H, W)
         return y.reshape(B, H2, W2, 2 * C)
@@ -403,7 +355,7 @@ class SwinTransformerBlock(nn.Module):
                                  l0.weight, l0.bias, l3.weight, l3.bias)
 
     def forward(self, x: Tensor) -> Tensor:
-        _require_cuda(x)
+        E.require_cuda(x)
         B, H, W, C = x.shape
         return self.run(x.to(torch.float32).contiguous().reshape(B * H * W, C), B, H, W).reshape(B, H, W, C)
 
@@ -460,7 +412,7 @@ class SwinTransformer(nn.Module):
                     nn.init.zeros_(m.bias)
 
     def forward(self, x: Tensor) -> Tensor:
-        _require_cuda(x)
+        E.require_cuda(x)
         B, _, Hi, Wi = x.shape
         p = self.patch_size
         if Hi % p or Wi % p:
@@ -470,14 +422,14 @@ class SwinTransformer(nn.Module):
         conv, norm0 = embed[0], embed[2]
         zeros = torch.zeros(H * W, conv.out_channels, device=x.device)
         t = PatchEmbedFn.apply(x, conv.weight, conv.bias, zeros, None, p, PATCH_CP1P2, None)     # [B, H*W, D] fp32
-        t = LayerNormFn.apply(t.reshape(B * H * W, -1), norm0.weight, norm0.bias, _ln_eps(norm0))
+        t = E.LayerNormFn.apply(t.reshape(B * H * W, -1), norm0.weight, norm0.bias, _ln_eps(norm0))
         for m in list(self.features)[1:]:
             if isinstance(m, PatchMerging):
                 t, H, W = m.run(t, B, H, W)
             else:
                 for blk in m:
                     t = blk.run(t, B, H, W)
-        t = LayerNormFn.apply(t, self.norm.weight, self.norm.bias, _ln_eps(self.norm))
+        t = E.LayerNormFn.apply(t, self.norm.weight, self.norm.bias, _ln_eps(self.norm))
         pooled = t.reshape(B, H * W, -1).mean(dim=1)                 # permute + AdaptiveAvgPool2d(1) + flatten (swin.py:694-697)
         return self.head(pooled)
 

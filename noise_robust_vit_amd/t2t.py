@@ -31,7 +31,7 @@ from torch import nn
 
 from . import encoder as E
 from . import kernels as K
-from ._lib import EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_DGELU, NrvError
+from ._lib import EPI_BIAS, EPI_BIAS_RESIDUAL, NrvError
 from .lucid_vit import Transformer
 
 MAX_KERNEL = 7
@@ -145,8 +145,7 @@ class _StageFn(torch.autograd.Function):
         x1 = K.gemm_nt(o, wo_b, out_dtype=torch.float32, epilogue=EPI_BIAS_RESIDUAL, bias=bo_p, aux=x)
         xn2, mean2, rstd2 = K.layernorm_pad_fwd(x1, C, P[2], P[3], eps)
         need = any(ctx.needs_input_grad)                    # grad mode is off inside forward: ask what the backward will want
-        u = torch.empty(B * N, Cp, dtype=torch.bfloat16, device=x.device) if need else None
-        h = K.gemm_nt(xn2, w1_b, out_dtype=torch.bfloat16, epilogue=EPI_BIAS_GELU, bias=b1_p, aux_out=u)
+        h, u = E.fc1_gelu(xn2, w1_b, b1_p, q8=False, save=need)
         y = K.gemm_nt(h, w2_b, out_dtype=torch.float32, epilogue=EPI_BIAS_RESIDUAL, bias=b2_p, aux=x1)
         ctx.meta, ctx.kind = meta, kind
         ctx.saved = (x, xn, mean1, rstd1, qkv, o, att, x1, xn2, mean2, rstd2, u, h, P, wqkv_t, wo_t, w1_t, w2_t)
@@ -163,7 +162,7 @@ class _StageFn(torch.autograd.Function):
         dy16 = K.cast_bf16(dy)
         # MLP half: y = x1 + W2 gelu(W1 LN(x1) + b1) + b2
         dw2, db2 = K.gemm_tn(dy16, h, want_dbias=True)
-        du = K.gemm_nt(dy16, w2_t, out_dtype=torch.bfloat16, epilogue=EPI_DGELU, aux=u)
+        du = E.dgelu_bwd(dy16, w2_t, u)
         dw1, db1 = K.gemm_tn(du, xn2, want_dbias=True)
         dxn2 = K.gemm_nt(du, w1_t, out_dtype=torch.bfloat16)
         dx1, dx1_16, dg2, dbt2 = K.layernorm_pad_bwd(dxn2, x1, C, P[2], mean2, rstd2, dres=dy, want_f32=True, want_bf16=True)

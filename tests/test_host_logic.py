@@ -87,14 +87,25 @@ def test_warmup_cosine_lr_matches_torch_schedulers():
         opt.step(); sched.step()
 
 
-def _imports(path):
+def _imports(path, package=None):
+    """Top-level modules the file imports; with `package` (the file's own package): the modules of that package it imports,
+    through relative imports or by the package's name.  Relative imports that climb out of the package (`from .. import x`,
+    level >= 2) are not followed: the package is flat, so there are none to see."""
     tree = ast.parse(open(path).read())
     out = set()
     for node in ast.walk(tree):
         if isinstance(node, ast.Import):
-            out |= {a.name.split(".")[0] for a in node.names}
-        elif isinstance(node, ast.ImportFrom) and node.module and node.level == 0:
-            out.add(node.module.split(".")[0])
+            names = [a.name for a in node.names]
+        elif isinstance(node, ast.ImportFrom) and node.level == 0 and node.module:
+            names = [node.module + "." + a.name for a in node.names] if package else [node.module]
+        elif isinstance(node, ast.ImportFrom) and node.level == 1 and package:
+            names = [".".join(filter(None, (package, node.module, a.name))) for a in node.names]
+        else:
+            continue
+        if package:
+            out |= {n.split(".")[1] for n in names if n.startswith(package + ".")}
+        else:
+            out |= {n.split(".")[0] for n in names}
     return out
 
 
@@ -125,6 +136,16 @@ def test_product_never_imports_the_oracle_or_reads_the_reference():
             for sub in ast.walk(node):
                 if isinstance(sub, ast.ImportFrom) and sub.module and sub.module.startswith("oracle"):
                     raise AssertionError(f"bench.py:{node.name} imports the oracle")
+
+
+def test_no_model_port_imports_another_model_port():
+    """Swin, LeViT, PatchConvNet, CaiT and T2T-ViT share host helpers through encoder.py only, so that an edit to one port
+    cannot break another.  t2t.py builds on lucid_vit.Transformer, as the reference's T2T builds on its ViT."""
+    ports = {"swin", "levit", "patch_convnet", "cait", "t2t"}
+    found = {p: _imports(os.path.join(ROOT, "noise_robust_vit_amd", p + ".py"), package="noise_robust_vit_amd") for p in ports}
+    assert all("encoder" in f for f in found.values())                     # relative imports are seen at all
+    crossing = {p: sorted(f & (ports - {p})) for p, f in found.items() if f & (ports - {p})}
+    assert not crossing, crossing
 
 
 def test_robust_flag_is_plumbed_not_substituted():

@@ -594,6 +594,48 @@ int nrv_attn_wide_fwd(const void* qkv_bf16, void* out_bf16, float* lse, int B, i
 int nrv_attn_wide_bwd(const void* qkv_bf16, const void* out_bf16, const void* dout_bf16, const float* lse,
                       void* dqkv_bf16, float* delta_ws, int B, int N, int H, int dh, float scale, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * RvT (ABI 18, added entry points; rvt.py).  Three memory-bound families: every lane moves 16 bytes, the arithmetic is fp32 in
+ * registers with ONE bf16 rounding on the store, every sum runs in a fixed order (no atomics): reruns are bit-identical.
+ * Shapes are checked first (NRV_ERR_SHAPE), then pointers (NRV_ERR_NULL), then alignment, all before any launch.
+ *
+ * 2-D axial rotary embedding (rvt.py:12-44, 130-147), in place on the packed qkv bf16 [B*N, 3*H*dh]:
+ *   nrv_rotary_fwd : for the token rows t >= lead of every sample (lead = 0 or 1 class rows) and the q block and the k block of
+ *                    every head, the first dr features are rotated pairwise: out[2m] = x[2m] c - x[2m+1] s, out[2m+1] =
+ *                    x[2m+1] c + x[2m] s with s / c = entry (t - lead, m) of the fp32 tables sin / cos [N - lead, dr / 2] (the
+ *                    reference's '(d j)' repeat is this pairing and is never materialised).  Features dr .. dh - 1, the class
+ *                    rows and the whole v block keep their bits.
+ *   nrv_rotary_bwd : the transposed rotation (s -> -s) on dqkv, same arguments.
+ *   dh % 8 == 0, dr % 2 == 0, 2 <= dr <= dh, lead in {0, 1}, N > lead; else NRV_ERR_SHAPE.  qkv and the tables 16-byte aligned.
+ * Depthwise ks x ks convolution, ks in {3, 5, 7}, stride 1, zero padding ks / 2, no bias, no activation (SpatialConv's
+ * DepthWiseConv2d.net[0], rvt.py:46-78) on token-major bf16 rows [B*(lead + H*W), C]: patch token (y, x) of sample b is row
+ * b*(lead + H*W) + lead + y*W + x.  The lead class rows of a sample are never read as neighbours.
+ *   nrv_dwconv_fwd : out(p) = bf16(sum_t w[c, t] a(p + off_t)), t = ky * ks + kx ascending; w fp32 [C, ks*ks] (the Conv2d weight
+ *                    [C, 1, ks, ks] viewed flat).  The class rows of out are NOT written.
+ *   nrv_dwconv_bwd : da = the gather of dout through the flipped taps, bf16, its class rows written as zeros; dw fp32
+ *                    [C, ks*ks] = per-sample partials (tokens in row-major order) summed over the samples in index order.
+ *                    workspace: nrv_dwconv_bwd_workspace(B, H, W, C, ks) bytes (the partials).
+ *   C % 8 == 0, B <= 65535, H * W <= 2^24, lead in {0, 1}; any H, W (planes smaller than the kernel radius included; planes
+ *   larger than the 14 x 14 token tile staged in LDS run several tiles); else NRV_ERR_SHAPE.
+ * GEGLU (rvt.py:80-83): u bf16 [rows, ld_u] holds [x | g] in its first 2 * hidden columns (the fc1 output with NRV_EPI_BIAS; the
+ * gate is the SECOND half).
+ *   nrv_geglu_fwd : h bf16 [rows, hidden] = bf16(x gelu_erf(g)).
+ *   nrv_geglu_bwd : du bf16 [rows, 2 * hidden]: du[:, :hidden] = dh gelu(g), du[:, hidden:] = dh x gelu'(g), both recomputed
+ *                   from u (no saved stream).
+ *   hidden % 8 == 0, ld_u >= 2 * hidden, ld_u % 8 == 0; else NRV_ERR_SHAPE.
+ * ---------------------------------------------------------------------------------------- */
+int nrv_rotary_fwd(void* qkv_bf16, const float* sin_t, const float* cos_t, int B, int N, int lead, int H, int dh, int dr,
+                   void* stream);
+int nrv_rotary_bwd(void* dqkv_bf16, const float* sin_t, const float* cos_t, int B, int N, int lead, int H, int dh, int dr,
+                   void* stream);
+int nrv_dwconv_fwd(const void* a, const float* w, void* out_bf16, int B, int H, int W, int lead, int C, int ks, void* stream);
+size_t nrv_dwconv_bwd_workspace(int B, int H, int W, int C, int ks);
+int nrv_dwconv_bwd(const void* a, const float* w, const void* dout, void* da_bf16, float* dw, void* workspace,
+                   size_t workspace_bytes, int B, int H, int W, int lead, int C, int ks, void* stream);
+int nrv_geglu_fwd(const void* u_bf16, int64_t ld_u, void* h_bf16, int64_t rows, int hidden, void* stream);
+int nrv_geglu_bwd(const void* u_bf16, int64_t ld_u, const void* dh_bf16, void* du_bf16, int64_t rows, int hidden,
+                  void* stream);
+
 /* CUs the GEMM launches leave free (process-wide; default 0; returns the previous value, or a negative error code when n is
  * negative or leaves fewer than 8 CUs).  The NT GEMM is persistent (one workgroup per CU for the whole launch) and the TN
  * GEMM sizes its token splits to one round of the CUs: with a collective's kernels resident on some CUs (RCCL all-reduce

@@ -1567,3 +1567,110 @@ def attn_wide_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, B: int, N
                                        delta.data_ptr(), B, N, H, dh, float(scale), _stream()),
          "nrv_attn_wide_bwd")
     return dqkv
+
+
+# ----------------------------------------------------------------------------------------------
+# RvT (ABI 18, added entry points): axial rotary embedding, plain depthwise ks x ks conv on rows with class rows, GEGLU
+# ----------------------------------------------------------------------------------------------
+def _rotary(fn: str, qkv: Tensor, sin: Tensor, cos: Tensor, B: int, N: int, lead: int, H: int, dh: int) -> Tensor:
+    _bf16(qkv, "qkv"); _f32(sin, "sin"); _f32(cos, "cos")
+    if not qkv.is_contiguous() or qkv.numel() != B * N * 3 * H * dh:
+        raise NrvError(f"{fn}: qkv must be contiguous [B*N, 3*H*dh]")
+    if sin.dim() != 2 or sin.shape != cos.shape or sin.shape[0] != N - lead or not (sin.is_contiguous() and cos.is_contiguous()):
+        raise NrvError(f"{fn}: sin / cos must be contiguous fp32 [{N - lead}, dr / 2], got {tuple(sin.shape)} / {tuple(cos.shape)}")
+    dr = 2 * sin.shape[1]
+    lib = _lib.load()
+    _run("rotary", 6.0 * B * (N - lead) * 2 * H * dr, 4.0 * B * (N - lead) * 2 * H * dr,
+         lambda: getattr(lib, fn)(qkv.data_ptr(), sin.data_ptr(), cos.data_ptr(), B, N, lead, H, dh, dr, _stream()), fn)
+    return qkv
+
+
+def rotary_fwd(qkv: Tensor, sin: Tensor, cos: Tensor, B: int, N: int, lead: int, H: int, dh: int) -> Tensor:
+    """In place on the packed qkv bf16 [B*N, 3*H*dh]: the first dr = 2 * sin.shape[1] features of q and k of every head are
+    rotated on the rows t >= lead; class rows, features >= dr and v keep their bits (include/nrv.h nrv_rotary_fwd)."""
+    return _rotary("nrv_rotary_fwd", qkv, sin, cos, B, N, lead, H, dh)
+
+
+def rotary_bwd(dqkv: Tensor, sin: Tensor, cos: Tensor, B: int, N: int, lead: int, H: int, dh: int) -> Tensor:
+    """The transposed rotation, in place on dqkv."""
+    return _rotary("nrv_rotary_bwd", dqkv, sin, cos, B, N, lead, H, dh)
+
+
+def _dwc_args(a: Tensor, w: Tensor, B: int, H: int, W: int, lead: int, name: str) -> Tuple[int, int, Tensor]:
+    _bf16(a, name); _f32(w, "w")
+    C = a.shape[-1]
+    if a.dim() != 2 or not a.is_contiguous() or a.shape[0] != B * (lead + H * W):
+        raise NrvError(f"{name} must be contiguous bf16 [{B * (lead + H * W)}, C], got {tuple(a.shape)}")
+    if w.numel() % C:
+        raise NrvError(f"w has {w.numel()} elements for {C} channels")
+    kk = w.numel() // C
+    ks = int(round(kk ** 0.5))
+    if ks * ks != kk:
+        raise NrvError(f"w must hold ks*ks taps per channel, got {kk}")
+    return C, ks, w.reshape(C, kk).contiguous()
+
+
+def dwconv_fwd(a: Tensor, w: Tensor, B: int, H: int, W: int, lead: int, out: Optional[Tensor] = None) -> Tensor:
+    """Depthwise ks x ks (3 / 5 / 7, stride 1, zero padding, no bias) on rows [B*(lead + H*W), C]; w fp32 [C, 1, ks, ks] or
+    [C, ks*ks].  The class rows of `out` are not written (a fresh `out` has zeros there)."""
+    C, ks, w2 = _dwc_args(a, w, B, H, W, lead, "a")
+    if out is None:
+        out = torch.zeros_like(a) if lead else torch.empty_like(a)
+    else:
+        _bf16(out, "out")
+        if out.shape != a.shape or not out.is_contiguous():
+            raise NrvError("dwconv_fwd: out must be contiguous with a's shape")
+    _run("dwconv_fwd", 2.0 * ks * ks * a.numel(), 4 * a.numel(),
+         lambda: _lib.load().nrv_dwconv_fwd(a.data_ptr(), w2.data_ptr(), out.data_ptr(), B, H, W, lead, C, ks, _stream()), "nrv_dwconv_fwd")
+    return out
+
+
+def dwconv_bwd(a: Tensor, w: Tensor, dout: Tensor, B: int, H: int, W: int, lead: int, da: Optional[Tensor] = None,
+               dw: Optional[Tensor] = None):
+    """(da bf16 like a, class rows zero; dw fp32 of w's shape)."""
+    C, ks, w2 = _dwc_args(a, w, B, H, W, lead, "a")
+    _dwc_args(dout, w, B, H, W, lead, "dout")
+    if dout.shape != a.shape:
+        raise NrvError("dwconv_bwd: dout must have a's shape")
+    if da is None:
+        da = torch.empty_like(a)
+    if dw is None:
+        dw = torch.empty(C, ks * ks, dtype=torch.float32, device=a.device)
+    _bf16(da, "da"); _f32(dw, "dw")
+    if da.shape != a.shape or not da.is_contiguous() or dw.numel() != C * ks * ks or not dw.is_contiguous():
+        raise NrvError("dwconv_bwd: da must be contiguous like a, dw contiguous with C*ks*ks elements")
+    lib = _lib.load()
+    ws = _workspace(lib.nrv_dwconv_bwd_workspace(B, H, W, C, ks), a.device)
+    _run("dwconv_bwd", 4.0 * ks * ks * a.numel(), 8 * a.numel(),
+         lambda: lib.nrv_dwconv_bwd(a.data_ptr(), w2.data_ptr(), dout.data_ptr(), da.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(),
+                                    B, H, W, lead, C, ks, _stream()), "nrv_dwconv_bwd")
+    return da, dw.reshape(w.shape)
+
+
+def geglu_fwd(u: Tensor, hidden: int) -> Tensor:
+    """h bf16 [rows, hidden] = u[:, :hidden] * gelu(u[:, hidden:2*hidden]); u bf16 with row stride >= 2 * hidden."""
+    _bf16(u, "u")
+    rows, cols, ld = _rows2d(u, "u")
+    if cols < 2 * hidden:
+        raise NrvError(f"geglu_fwd: u has {cols} columns, needs {2 * hidden}")
+    h = torch.empty(rows, hidden, dtype=torch.bfloat16, device=u.device)
+    _run("geglu_fwd", 0.0, 6 * rows * hidden,
+         lambda: _lib.load().nrv_geglu_fwd(u.data_ptr(), ld, h.data_ptr(), rows, hidden, _stream()), "nrv_geglu_fwd")
+    return h
+
+
+def geglu_bwd(u: Tensor, dh: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """du bf16 [rows, 2*hidden] from dh bf16 [rows, hidden], gelu and gelu' recomputed from u."""
+    _bf16(u, "u"); _bf16(dh, "dh")
+    rows, cols, ld = _rows2d(u, "u")
+    hidden = dh.shape[1]
+    if not dh.is_contiguous() or dh.shape[0] != rows or cols < 2 * hidden:
+        raise NrvError(f"geglu_bwd: dh must be contiguous [{rows}, hidden] with 2 * hidden <= {cols}")
+    if out is None:
+        out = torch.empty(rows, 2 * hidden, dtype=torch.bfloat16, device=u.device)
+    _bf16(out, "out")
+    if tuple(out.shape) != (rows, 2 * hidden) or not out.is_contiguous():
+        raise NrvError("geglu_bwd: out must be contiguous [rows, 2 * hidden]")
+    _run("geglu_bwd", 0.0, 10 * rows * hidden,
+         lambda: _lib.load().nrv_geglu_bwd(u.data_ptr(), ld, dh.data_ptr(), out.data_ptr(), rows, hidden, _stream()), "nrv_geglu_bwd")
+    return out

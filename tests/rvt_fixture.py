@@ -1,0 +1,79 @@
+"""Weights, inputs and cases of the RvT fixture (tests/golden/rvt_small.npz), rebuilt from seeds on both sides.
+
+tests/golden/gen_golden_rvt.py loads these into the reference's rvt.py modules and stores what the reference computes (logits,
+CE loss, the gradient of every parameter) plus the module trees; the tests load the same tensors into the HIP modules and into
+tests/rvt_ref.py.  Seeds, packing and gradient sampling are swin_fixture's.
+"""
+import torch
+
+from swin_fixture import _gen, grad_index, grad_sample, pack, pack_grads, pack_tree, unpack, unpack_grads, unpack_tree  # noqa: F401
+
+SMALL = dict(image_size=48, patch_size=8, num_classes=10, dim=64, depth=2, heads=2, dim_head=32, mlp_dim=96)
+ONE = dict(SMALL, depth=1)
+# name -> (model config, robust, train, batch)
+CASES = {
+    "s_train": (SMALL, False, True, 3),                                   # 37 tokens; dim == inner: Identity class projection; head dim 32
+    "s_eval": (SMALL, False, False, 3),
+    "proj": (dict(ONE, dim=48), False, True, 2),                          # cls_proj = Linear(48, 64)
+    "norot": (dict(ONE, use_rotary=False), False, True, 2),
+    "noconv": (dict(ONE, use_ds_conv=False), False, True, 2),
+    "noglu": (dict(ONE, use_glu=False), False, True, 2),
+    "plain": (dict(ONE, use_rotary=False, use_ds_conv=False, use_glu=False), False, True, 2),
+    "dh64": (dict(ONE, image_size=32, dim=128, dim_head=64), False, True, 2),      # 17 tokens, single-pass attention
+    "g1": (dict(ONE, image_size=8), False, True, 3),                      # 1 x 1 grid: 5 x 5 conv on one token, rotary coordinate -1
+    "g224": (dict(ONE, image_size=224, patch_size=16), False, True, 1),   # 197 tokens, the real grid
+    "r_train": (dict(ONE, dim=128, dim_head=64), True, True, 2),          # fused Sinkhorn
+    "r_comp": (ONE, True, True, 2),                                       # Sinkhorn at head dim 32: the composed path
+}
+# seeded init (torch.manual_seed(0)) of one full-size configuration: RvT-S-like at 224 px, 100 classes
+FULL = dict(image_size=224, patch_size=16, num_classes=100, dim=384, depth=12, heads=6, mlp_dim=768)
+# stored entries of the reference's AxialRotaryEmbedding / rotate_every_two: (grid, dim, max_freq)
+ROTARY_PROBES = ((3, 32, 48), (1, 32, 8), (14, 64, 224), (2, 24, 10))
+
+
+def build(module, case: str, sinkhorn=None):
+    """The case's model from `module` (the reference's rvt or noise_robust_vit_amd.rvt).  The reference's RvT has no `robust`
+    argument: there `attend` of every Attention is replaced with `sinkhorn()` (utils.SinkhornAttention)."""
+    cfg, robust, train, _ = CASES[case]
+    try:
+        m = module.RvT(**cfg, robust=robust)
+    except TypeError:
+        m = module.RvT(**cfg)
+        if robust:
+            for attn, _ in m.transformer.layers:
+                attn.fn.attend = sinkhorn()
+    return m.train(train)
+
+
+def weights(model, seed: int) -> dict:
+    """Linear / Conv2d weights ~ N(0, 1/fan_in); LayerNorm weights 1 + 0.1 N(0, 1); cls_token 0.5 N(0, 1); biases 0.02 N(0, 1);
+    the rotary `scales` buffer keeps the module's value."""
+    out = {}
+    for name, t in model.state_dict().items():
+        if name.endswith("pos_emb.scales"):
+            out[name] = t.clone()
+            continue
+        z = torch.randn(tuple(t.shape), generator=_gen(seed, name))
+        leaf = name.rsplit(".", 1)[-1]
+        if name == "cls_token":
+            z = 0.5 * z
+        elif t.dim() >= 2:
+            z = z / t[0].numel() ** 0.5
+        elif leaf == "weight":
+            z = 1.0 + 0.1 * z
+        else:
+            z = 0.02 * z
+        out[name] = z
+    return out
+
+
+def inputs(case: str):
+    cfg, _, _, B = CASES[case]
+    g = _gen(17, "inputs." + case)
+    img = torch.randn(B, cfg.get("channels", 3), cfg["image_size"], cfg["image_size"], generator=g)
+    y = torch.randint(0, cfg["num_classes"], (B,), generator=g)
+    return img, y
+
+
+def rotary_probe_input(n: int, dim: int) -> torch.Tensor:
+    return torch.randn(1, n * n, dim, generator=_gen(23, f"rotary.{n}.{dim}"))

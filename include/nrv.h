@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NRV_ABI_VERSION 18
+#define NRV_ABI_VERSION 19
 
 /* dtype codes */
 #define NRV_F32 0
@@ -477,6 +477,22 @@ int nrv_bgemm(const void* A, int a_dtype, int64_t a_rs, int64_t a_cs, int64_t a_
               const void* B, int b_dtype, int64_t b_rs, int64_t b_cs, int64_t b_b1, int64_t b_b2,
               void* C, int c_dtype, int64_t c_rs, int64_t c_cs, int64_t c_b1, int64_t c_b2,
               int G1, int G2, int M, int N, int K, float alpha, void* stream);
+
+/* Launch-plan query of nrv_bgemm (ABI 19).  Read-only like nrv_gemm_nt_plan: it launches nothing, reads no memory and is
+ * callable without a GPU; the pointers are only inspected for alignment.  nrv_bgemm takes every host-side decision from the
+ * same function, so the answer is the launch's own, and the return code is the one nrv_bgemm gives for the same arguments
+ * (NRV_ERR_NULL also for a null `plan`; NRV_ERR_SHAPE for a non-positive dimension or more than 2^31 - 1 workgroups;
+ * NRV_ERR_DTYPE).
+ *   a_vec, b_vec : the operand is staged by 16-byte vectors (8 bf16 / 4 fp32) along its unit stride: one of its two matrix strides
+ *                  is 1 and the address is dword-aligned (bf16: not both strides 1, and the other matrix stride and both batch
+ *                  strides even); 0 = element by element.  Two vector operands run the register-double-buffered K loop.
+ *   c_vec        : 4 consecutive columns of a C row go out as one store (c_cs == 1, dword-aligned base; bf16: c_rs, c_b1, c_b2 even).
+ *   tiles_m, tiles_n : 64 x 64 tiles of C;  blocks = tiles_m * tiles_n * G1 * G2 workgroups. */
+typedef struct { int a_vec, b_vec, c_vec, tiles_m, tiles_n; long long blocks; } nrv_bgemm_plan_t;
+int nrv_bgemm_plan(const void* A, int a_dtype, int64_t a_rs, int64_t a_cs, int64_t a_b1, int64_t a_b2,
+                   const void* B, int b_dtype, int64_t b_rs, int64_t b_cs, int64_t b_b1, int64_t b_b2,
+                   const void* C, int c_dtype, int64_t c_rs, int64_t c_cs, int64_t c_b1, int64_t c_b2,
+                   int G1, int G2, int M, int N, int K, nrv_bgemm_plan_t* plan);
 
 /* ------------------------------------------------------------------------------------------
  * Patch unfold (replaces einops Rearrange 'b c (h p1) (w p2) -> b h w (p1 p2 c)' simple_vit.py:126-129,

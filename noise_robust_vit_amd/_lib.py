@@ -18,7 +18,7 @@ LIB_PATH = _DEFAULT_LIB       # no environment override: what runs is the in-tre
 NRV_F32, NRV_BF16, NRV_U8 = 0, 1, 2
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_DGELU, EPI_BIAS_GELU_Q8, EPI_DGELU_Q8 = 0, 1, 2, 3, 4, 5, 6
 PATCH_P1P2C, PATCH_CP1P2 = 0, 1
-ABI_VERSION = 18
+ABI_VERSION = 19
 ATTN_QKV_BLOCKED, ATTN_OUT_BLOCKED = 1, 2      # include/nrv.h: NRV_ATTN_*_BLOCKED
 CONV_NCHW, CONV_NHWC = 0, 1                    # include/nrv.h: NRV_CONV_*
 SPLIT_NCHW, SPLIT_ROWS = 0, 1                  # include/nrv.h: NRV_SPLIT_*
@@ -39,6 +39,11 @@ class TnPlan(ctypes.Structure):
     """include/nrv.h `nrv_tn_plan`: what nrv_gemm_tn_bf16 would launch."""
     _fields_ = [("tiles", c_int), ("splits", c_int), ("kt_q", c_int), ("kt_r", c_int), ("phased", c_int), ("direct", c_int),
                 ("reduce", c_int)]
+
+class BgemmPlan(ctypes.Structure):
+    """include/nrv.h `nrv_bgemm_plan_t`: what nrv_bgemm would launch."""
+    _fields_ = [("a_vec", c_int), ("b_vec", c_int), ("c_vec", c_int), ("tiles_m", c_int), ("tiles_n", c_int),
+                ("blocks", ctypes.c_longlong)]
 
 
 # name -> (restype, argtypes); every symbol include/nrv.h declares (tests/test_abi.py checks the two agree)
@@ -154,6 +159,8 @@ SIGNATURES = {
                                   c_void_p]),
     "nrv_bgemm": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64,
                           c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "nrv_bgemm_plan": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64,
+                               c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "nrv_rotary_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "nrv_rotary_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "nrv_dwconv_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),

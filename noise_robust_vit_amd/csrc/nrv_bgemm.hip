@@ -280,31 +280,54 @@ int bg_vec_ok(const void* ptr, int f32, int64_t s_row, int64_t s_k, int64_t b1, 
     return (reinterpret_cast<uintptr_t>(ptr) & 3u) == 0 && !(other & 1) && !(b1 & 1) && !(b2 & 1);
 }
 
-}  // namespace
-
-extern "C" int nrv_bgemm(const void* A, int a_dtype, int64_t a_rs, int64_t a_cs, int64_t a_b1, int64_t a_b2,
-                         const void* B, int b_dtype, int64_t b_rs, int64_t b_cs, int64_t b_b1, int64_t b_b2,
-                         void* C, int c_dtype, int64_t c_rs, int64_t c_cs, int64_t c_b1, int64_t c_b2,
-                         int G1, int G2, int M, int N, int K, float alpha, void* stream) {
-    if (!A || !B || !C) return NRV_ERR_NULL;
+// Every host-side decision of a launch, for nrv_bgemm and nrv_bgemm_plan alike: the refusals, the tile grid and which operands /
+// C rows take vectors.  Pointers are only inspected for alignment.
+int bg_plan(const void* A, int a_dtype, int64_t a_rs, int64_t a_cs, int64_t a_b1, int64_t a_b2,
+            const void* B, int b_dtype, int64_t b_rs, int64_t b_cs, int64_t b_b1, int64_t b_b2,
+            const void* C, int c_dtype, int64_t c_rs, int64_t c_cs, int64_t c_b1, int64_t c_b2,
+            int G1, int G2, int M, int N, int K, nrv_bgemm_plan_t* pl) {
+    if (!A || !B || !C || !pl) return NRV_ERR_NULL;
     if (G1 <= 0 || G2 <= 0 || M <= 0 || N <= 0 || K <= 0) return NRV_ERR_SHAPE;
     for (int d : {a_dtype, b_dtype, c_dtype})
         if (d != NRV_F32 && d != NRV_BF16) return NRV_ERR_DTYPE;
     const long long tiles_m = nrv_cdiv(M, BG_T), tiles_n = nrv_cdiv(N, BG_T);
     const long long blocks = tiles_m * tiles_n * (long long)G1 * G2;
     if (blocks > 0x7fffffffll) return NRV_ERR_SHAPE;
+    const int c_f32 = c_dtype == NRV_F32;
+    pl->tiles_m = (int)tiles_m; pl->tiles_n = (int)tiles_n; pl->blocks = blocks;
+    pl->a_vec = bg_vec_ok(A, a_dtype == NRV_F32, a_rs, a_cs, a_b1, a_b2);
+    pl->b_vec = bg_vec_ok(B, b_dtype == NRV_F32, b_cs, b_rs, b_b1, b_b2);
+    // 4 consecutive columns of a C row as one store: dword-aligned addresses (bf16: even row / batch strides; tile origins are multiples of 4)
+    pl->c_vec = c_cs == 1 && (reinterpret_cast<uintptr_t>(C) & 3u) == 0 && (c_f32 || (!(c_rs & 1) && !(c_b1 & 1) && !(c_b2 & 1)));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int nrv_bgemm_plan(const void* A, int a_dtype, int64_t a_rs, int64_t a_cs, int64_t a_b1, int64_t a_b2,
+                              const void* B, int b_dtype, int64_t b_rs, int64_t b_cs, int64_t b_b1, int64_t b_b2,
+                              const void* C, int c_dtype, int64_t c_rs, int64_t c_cs, int64_t c_b1, int64_t c_b2,
+                              int G1, int G2, int M, int N, int K, nrv_bgemm_plan_t* plan) {
+    return bg_plan(A, a_dtype, a_rs, a_cs, a_b1, a_b2, B, b_dtype, b_rs, b_cs, b_b1, b_b2, C, c_dtype, c_rs, c_cs, c_b1, c_b2,
+                   G1, G2, M, N, K, plan);
+}
+
+extern "C" int nrv_bgemm(const void* A, int a_dtype, int64_t a_rs, int64_t a_cs, int64_t a_b1, int64_t a_b2,
+                         const void* B, int b_dtype, int64_t b_rs, int64_t b_cs, int64_t b_b1, int64_t b_b2,
+                         void* C, int c_dtype, int64_t c_rs, int64_t c_cs, int64_t c_b1, int64_t c_b2,
+                         int G1, int G2, int M, int N, int K, float alpha, void* stream) {
+    nrv_bgemm_plan_t pl;
+    if (const int rc = bg_plan(A, a_dtype, a_rs, a_cs, a_b1, a_b2, B, b_dtype, b_rs, b_cs, b_b1, b_b2, C, c_dtype, c_rs, c_cs, c_b1, c_b2,
+                               G1, G2, M, N, K, &pl)) return rc;
     BgParams p;
     p.A = BgOperand{A, a_rs, a_cs, a_b1, a_b2, a_dtype == NRV_F32};
     p.B = BgOperand{B, b_rs, b_cs, b_b1, b_b2, b_dtype == NRV_F32};
     p.C = C; p.c_rs = c_rs; p.c_cs = c_cs; p.c_b1 = c_b1; p.c_b2 = c_b2; p.c_f32 = c_dtype == NRV_F32;
     p.G2 = G2; p.M = M; p.N = N; p.K = K;
-    p.tiles_m = (int)tiles_m; p.tiles_n = (int)tiles_n;
+    p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n;
     p.alpha = alpha;
-    p.a_vec = bg_vec_ok(A, p.A.f32, a_rs, a_cs, a_b1, a_b2);
-    p.b_vec = bg_vec_ok(B, p.B.f32, b_cs, b_rs, b_b1, b_b2);
-    // 4 consecutive columns of a C row as one store: dword-aligned addresses (bf16: even row / batch strides; tile origins are multiples of 4)
-    p.c_vec = c_cs == 1 && (reinterpret_cast<uintptr_t>(C) & 3u) == 0 && (p.c_f32 || (!(c_rs & 1) && !(c_b1 & 1) && !(c_b2 & 1)));
-    hipLaunchKernelGGL(bgemm_kernel, dim3((unsigned)blocks), dim3(BG_THREADS), 0, static_cast<hipStream_t>(stream), p);
+    p.a_vec = pl.a_vec; p.b_vec = pl.b_vec; p.c_vec = pl.c_vec;
+    hipLaunchKernelGGL(bgemm_kernel, dim3((unsigned)pl.blocks), dim3(BG_THREADS), 0, static_cast<hipStream_t>(stream), p);
     NRV_CHECK_LAUNCH();
     return 0;
 }

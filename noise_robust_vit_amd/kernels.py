@@ -534,6 +534,24 @@ def bgemm(A, a_str, B_, b_str, C, c_str, G1: int, G2: int, M: int, N: int, K: in
          "nrv_bgemm")
 
 
+def bgemm_plan(A, a_str, B_, b_str, C, c_str, G1: int, G2: int, M: int, N: int, K: int) -> dict:
+    """What `bgemm` would launch for these arguments (include/nrv.h nrv_bgemm_plan): which operands are staged by 16-byte vectors,
+    whether C rows take vector stores, the tile grid and the workgroup count.  Operands as in `bgemm`, (tensor, element offset)
+    pairs, or (address of element 0, torch dtype) pairs: only the alignment of an address enters the plan, so a made-up one
+    will do.  Read-only; needs no GPU.  Raises NrvError where `nrv_bgemm` would refuse the launch."""
+    args = []
+    for (t, off), st, name in ((A, a_str, "A"), (B_, b_str, "B"), (C, c_str, "C")):
+        if isinstance(t, Tensor):
+            args += [t.data_ptr() + int(off) * t.element_size(), _dt(t, name)]
+        else:
+            args += [int(t), _dt(torch.empty(0, dtype=off), name)]
+        args += [int(v) for v in st]
+    pl = _lib.BgemmPlan()
+    check(_lib.load().nrv_bgemm_plan(*args, int(G1), int(G2), int(M), int(N), int(K), ctypes.addressof(pl)), "nrv_bgemm_plan")
+    return {"a_vec": bool(pl.a_vec), "b_vec": bool(pl.b_vec), "c_vec": bool(pl.c_vec), "tiles_m": pl.tiles_m, "tiles_n": pl.tiles_n,
+            "blocks": pl.blocks}
+
+
 def _composed_strides(N: int, H: int, dh: int):
     """(row, col, batch, head) element strides of one head's [N, dh] slice of q, k or v inside qkv [B*N, 3*H*dh] (and read
     transposed), of one head's slice of out / dout [B*N, H*dh], and of one head's [N, N] block of a [B,H,N,N] matrix (and transposed)."""

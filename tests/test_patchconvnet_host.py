@@ -177,7 +177,7 @@ def test_trunc_normal_draws_like_the_reference():
 def test_abi17_prototypes_in_header_binding_and_exports():
     from noise_robust_vit_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "nrv.h")).read()
-    assert re.search(r"#define NRV_ABI_VERSION 18\b", hdr) and _lib.ABI_VERSION == 18
+    assert re.search(r"#define NRV_ABI_VERSION 19\b", hdr) and _lib.ABI_VERSION == 19
     for name in NEW:
         assert re.search(r"\b" + name + r"\s*\(", hdr), name
         assert name in _lib.SIGNATURES, name
@@ -186,4 +186,4 @@ def test_abi17_prototypes_in_header_binding_and_exports():
     lib = ctypes.CDLL(build.build())
     for name in NEW:
         assert hasattr(lib, name), name
-    assert lib.nrv_abi_version() == 18
+    assert lib.nrv_abi_version() == 19

@@ -170,7 +170,7 @@ def test_new_prototypes_are_declared_bound_and_exported():
         assert re.search(r"\b" + name + r"\s*\(", code), name
         assert name in _lib.SIGNATURES, name
         assert hasattr(handle, name), name
-    assert handle.nrv_abi_version() == 18 == _lib.ABI_VERSION
+    assert handle.nrv_abi_version() == 19 == _lib.ABI_VERSION
     assert "nrv_rvt.hip" in build.SOURCES
     from noise_robust_vit_amd import kernels as K
     for name in ("rotary_fwd", "rotary_bwd", "dwconv_fwd", "dwconv_bwd", "geglu_fwd", "geglu_bwd"):

@@ -652,6 +652,37 @@ int nrv_geglu_fwd(const void* u_bf16, int64_t ld_u, void* h_bf16, int64_t rows, 
 int nrv_geglu_bwd(const void* u_bf16, int64_t ld_u, const void* dh_bf16, void* du_bf16, int64_t rows, int hidden,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * PiT (added to ABI 19 without changing an existing prototype, so the version number stays; pit.py).
+ *
+ * Pooled depthwise convolution (Pool.downsample.net[0], pit.py:90-106): Conv2d(C, 2C, 3, stride 2, padding 1, groups = C, bias)
+ * on token-major rows of the fp32 residual stream x [B*(lead + H*W), C], lead = 0 or 1 class rows in front of every sample's
+ * plane (never read as neighbours).  Output planes are Ho = (H - 1) / 2 + 1 by Wo = (W - 1) / 2 + 1; output channel o reads
+ * input channel o / 2 (PyTorch's grouping).  w fp32 [2C, 9] (the Conv2d weight [2C, 1, 3, 3] viewed flat), bias fp32 [2C].
+ *   nrv_pool_dwconv_fwd : out bf16 [B*Ho*Wo, 2C], dense, no class rows (the A operand of the 1 x 1 convolution's GEMM):
+ *                         out = bf16(bias[o] + sum_t w[o, t] x(2 oy - 1 + ky, 2 ox - 1 + kx, o / 2)), t = 3 ky + kx ascending,
+ *                         fp32 in registers, one rounding.
+ *   nrv_pool_dwconv_bwd : dx fp32 [B*(lead + H*W), C] in gather form: every input element sums the at most 2 x 2 windows that
+ *                         cover it times the two output channels of its group, ky then kx then o = 2c, 2c + 1 ascending; the
+ *                         class rows of dx are written as zeros.  dw fp32 [2C, 9] and dbias fp32 [2C] = per-sample partials
+ *                         (output tokens in row-major order) summed over the samples in index order.  No atomics.
+ *                         workspace: nrv_pool_dwconv_bwd_workspace(B, H, W, C) bytes (the partials).
+ *   C % 8 == 0, B <= 65535, H * W <= 2^24, lead in {0, 1}, any H, W >= 1; else NRV_ERR_SHAPE.  Shapes are checked first, then
+ *   pointers (NRV_ERR_NULL), then the workspace size and the 16-byte alignment of every pointer, all before any launch.
+ * Overlapped patch unfold (to_patch_embedding[0]):
+ *   nrv_unfold_patches : nn.Unfold(ks, stride) on an NCHW image (fp32 | bf16), no padding, 1 <= stride <= ks <= 32.  cols bf16
+ *                        [B*Ho*Wo, KP], feature c ks^2 + ky ks + kx, KP = ks^2 C rounded up to 8, columns >= ks^2 C zeros.
+ *                        fp32 sources are rounded to nearest even, bf16 sources are copied.  The kernel of nrv_soft_split_fwd
+ *                        (which keeps ks <= 7).  cols 16-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+int nrv_pool_dwconv_fwd(const float* x_f32, const float* w, const float* bias, void* out_bf16, int B, int H, int W, int lead, int C,
+                        void* stream);
+size_t nrv_pool_dwconv_bwd_workspace(int B, int H, int W, int C);
+int nrv_pool_dwconv_bwd(const float* x_f32, const float* w, const void* dout_bf16, float* dx_f32, float* dw, float* dbias,
+                        void* workspace, size_t workspace_bytes, int B, int H, int W, int lead, int C, void* stream);
+int nrv_unfold_patches(const void* img, int img_dtype, void* cols_bf16, int B, int C, int H, int W, int ks, int stride,
+                       void* stream);
+
 /* CUs the GEMM launches leave free (process-wide; default 0; returns the previous value, or a negative error code when n is
  * negative or leaves fewer than 8 CUs).  The NT GEMM is persistent (one workgroup per CU for the whole launch) and the TN
  * GEMM sizes its token splits to one round of the CUs: with a collective's kernels resident on some CUs (RCCL all-reduce

@@ -16,6 +16,8 @@ from . import t2t  # noqa: F401
 from .t2t import RearrangeImage, T2TViT, conv_output_size  # noqa: F401
 from . import rvt  # noqa: F401
 from .rvt import RvT  # noqa: F401
+from . import pit  # noqa: F401
+from .pit import PiT  # noqa: F401
 
 
 
@@ -30,4 +32,4 @@ def invalidate_weight_cache() -> None:
 __all__ = ["invalidate_weight_cache", "SimpleViT", "Attention", "FeedForward", "Transformer", "SinkhornAttention",
            "VisionTransformer", "vit_s_16", "vit_b_16", "vit_b_32", "vit_l_16", "vit_l_32",
            "SwinTransformer", "swin_t", "swin_s", "swin_b", "levit", "patch_convnet", "cait",
-           "t2t", "T2TViT", "RearrangeImage", "conv_output_size", "rvt", "RvT"]
+           "t2t", "T2TViT", "RearrangeImage", "conv_output_size", "rvt", "RvT", "pit", "PiT"]

@@ -169,6 +169,11 @@ SIGNATURES = {
                                c_int, c_int, c_void_p]),
     "nrv_geglu_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),
     "nrv_geglu_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "nrv_pool_dwconv_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "nrv_pool_dwconv_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "nrv_pool_dwconv_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
+                                    c_int, c_int, c_int, c_void_p]),
+    "nrv_unfold_patches": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "nrv_set_reserved_cus": (c_int, [c_int]),
     "nrv_probe": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p]),
 }

@@ -251,7 +251,8 @@ __global__ __launch_bounds__(64) void probe_kernel(int which, const bf16_t* __re
 // unfold (im2col) and its fold, one kernel pair with two feature orders:
 //   tap-major     (ky, kx, c): convolution as unfold + GEMM (LeViT's b16 stem, levit.py:166-175: Conv2d(3x3, stride 2, pad 1)
 //                              without bias; the PatchConvNet stem), nrv_conv_unfold / nrv_conv_fold
-//   channel-major (c, ky, kx): nn.Unfold's order, the soft split of T2T-ViT (t2t.py:58-93), nrv_soft_split_fwd / _bwd
+//   channel-major (c, ky, kx): nn.Unfold's order, the soft split of T2T-ViT (t2t.py:58-93), nrv_soft_split_fwd / _bwd, and the
+//                              overlapping patches of PiT (pit.py:144-148; ks up to 32, no fold), nrv_unfold_patches
 //   unfold: src (NCHW image, fp32 | bf16, or bf16 token rows [B*H*W, ld]: NHWC, the 'b (h w) c -> b c h w' of RearrangeImage is
 //           the addressing) -> cols bf16 [B*Ho*Wo, KP], KP = ks*ks*C rounded up to 8; taps outside the image and columns
 //           >= ks*ks*C are zero.  fp32 sources are rounded once (nearest even), bf16 sources are copied.  One thread = 8
@@ -349,9 +350,10 @@ __global__ __launch_bounds__(256) void fold_kernel(const bf16_t* __restrict__ dc
     }
 }
 
-// the shape rules of the four unfold / fold entry points; fills g
-int unfold_geom(UnfoldGeom& g, int B, int C, int H, int W, int ks, int stride, int pad, long long ld) {
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ks <= 0 || ks > 7 || stride <= 0 || pad < 0 || pad >= ks) return NRV_ERR_SHAPE;
+// the shape rules of the unfold / fold entry points; fills g.  max_ks: 7 for the convolutions and the soft split, 32 for the
+// overlapped patches of PiT
+int unfold_geom(UnfoldGeom& g, int B, int C, int H, int W, int ks, int stride, int pad, long long ld, int max_ks = 7) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ks <= 0 || ks > max_ks || stride <= 0 || pad < 0 || pad >= ks) return NRV_ERR_SHAPE;
     if (H + 2 * pad < ks || W + 2 * pad < ks) return NRV_ERR_SHAPE;
     g.B = B; g.C = C; g.H = H; g.W = W; g.ks = ks; g.stride = stride; g.pad = pad; g.ld = ld;
     g.Ho = (H + 2 * pad - ks) / stride + 1;
@@ -463,6 +465,19 @@ extern "C" int nrv_soft_split_bwd(const void* dcols_bf16, float* dx, int64_t ld_
     if (ld_dx < C) return NRV_ERR_SHAPE;
     if (!dcols_bf16 || !dx) return NRV_ERR_NULL;
     launch_fold<UF_CHANNEL_MAJOR, true>(dcols_bf16, dx, g, SPLIT_GRID_CAP, static_cast<hipStream_t>(stream));
+    NRV_CHECK_LAUNCH();
+    return 0;
+}
+
+// nn.Unfold(ks, stride) of PiT's to_patch_embedding[0]: the channel-major unfold with ks up to 32, no padding, stride <= ks
+extern "C" int nrv_unfold_patches(const void* img, int img_dtype, void* cols_bf16, int B, int C, int H, int W, int ks, int stride,
+                                  void* stream) {
+    UnfoldGeom g{};
+    if (unfold_geom(g, B, C, H, W, ks, stride, 0, C, 32) || stride > ks) return NRV_ERR_SHAPE;
+    if (!img || !cols_bf16) return NRV_ERR_NULL;
+    if (img_dtype != NRV_F32 && img_dtype != NRV_BF16) return NRV_ERR_DTYPE;
+    if (!nrv_aligned16(cols_bf16)) return NRV_ERR_ALIGN;
+    launch_unfold<UF_CHANNEL_MAJOR>(false, img_dtype == NRV_F32, img, cols_bf16, g, SPLIT_GRID_CAP, static_cast<hipStream_t>(stream));
     NRV_CHECK_LAUNCH();
     return 0;
 }

@@ -1692,3 +1692,80 @@ def geglu_bwd(u: Tensor, dh: Tensor, out: Optional[Tensor] = None) -> Tensor:
     _run("geglu_bwd", 0.0, 10 * rows * hidden,
          lambda: _lib.load().nrv_geglu_bwd(u.data_ptr(), ld, dh.data_ptr(), out.data_ptr(), rows, hidden, _stream()), "nrv_geglu_bwd")
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# PiT (added to ABI 19): the Pool layer's stride-2 depthwise conv on the fp32 stream, nn.Unfold with overlapping patches
+# ----------------------------------------------------------------------------------------------
+def pool_out_size(n: int) -> int:
+    return (n - 1) // 2 + 1
+
+
+def _pool_args(x: Tensor, w: Tensor, B: int, H: int, W: int, lead: int, fn: str) -> Tuple[int, Tensor]:
+    _f32(x, "x"); _f32(w, "w")
+    if x.dim() != 2 or not x.is_contiguous() or x.shape[0] != B * (lead + H * W):
+        raise NrvError(f"{fn}: x must be contiguous fp32 [{B * (lead + H * W)}, C], got {tuple(x.shape)}")
+    C = x.shape[1]
+    if w.numel() != 18 * C:
+        raise NrvError(f"{fn}: w has {w.numel()} elements, expected [2C, 9] = {18 * C}")
+    return C, w.reshape(2 * C, 9).contiguous()
+
+
+def _out_buffer(t: Optional[Tensor], shape, dtype, device, name: str) -> Tensor:
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _dev(t, name)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise NrvError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def pool_dwconv_fwd(x: Tensor, w: Tensor, bias: Tensor, B: int, H: int, W: int, lead: int, out: Optional[Tensor] = None) -> Tensor:
+    """Conv2d(C, 2C, 3, stride 2, padding 1, groups = C, bias) on the fp32 rows x [B*(lead + H*W), C] -> bf16 [B*Ho*Wo, 2C]
+    without class rows; w fp32 [2C, 1, 3, 3] or [2C, 9], bias fp32 [2C] (include/nrv.h nrv_pool_dwconv_fwd)."""
+    C, w2 = _pool_args(x, w, B, H, W, lead, "pool_dwconv_fwd")
+    _f32(bias, "bias")
+    if bias.numel() != 2 * C or not bias.is_contiguous():
+        raise NrvError(f"pool_dwconv_fwd: bias must be contiguous [{2 * C}]")
+    Ho, Wo = pool_out_size(H), pool_out_size(W)
+    out = _out_buffer(out, (B * Ho * Wo, 2 * C), torch.bfloat16, x.device, "out")
+    _run("pool_dwconv_fwd", 18.0 * out.numel(), 4 * x.numel() + 2 * out.numel(),
+         lambda: _lib.load().nrv_pool_dwconv_fwd(x.data_ptr(), w2.data_ptr(), bias.data_ptr(), out.data_ptr(), B, H, W, lead, C, _stream()),
+         "nrv_pool_dwconv_fwd")
+    return out
+
+
+def pool_dwconv_bwd(x: Tensor, w: Tensor, dout: Tensor, B: int, H: int, W: int, lead: int, dx: Optional[Tensor] = None,
+                    dw: Optional[Tensor] = None, dbias: Optional[Tensor] = None):
+    """(dx fp32 like x with zero class rows, dw fp32 of w's shape, dbias fp32 [2C]) from dout bf16 [B*Ho*Wo, 2C]."""
+    C, w2 = _pool_args(x, w, B, H, W, lead, "pool_dwconv_bwd")
+    _bf16(dout, "dout")
+    Ho, Wo = pool_out_size(H), pool_out_size(W)
+    if not dout.is_contiguous() or tuple(dout.shape) != (B * Ho * Wo, 2 * C):
+        raise NrvError(f"pool_dwconv_bwd: dout is {tuple(dout.shape)}, expected a contiguous [{B * Ho * Wo}, {2 * C}]")
+    dx = _out_buffer(dx, x.shape, torch.float32, x.device, "dx")
+    dw = _out_buffer(dw, (2 * C, 9), torch.float32, x.device, "dw")
+    db = _out_buffer(dbias, (2 * C,), torch.float32, x.device, "dbias")
+    lib = _lib.load()
+    ws = _workspace(lib.nrv_pool_dwconv_bwd_workspace(B, H, W, C), x.device)
+    _run("pool_dwconv_bwd", 54.0 * dout.numel(), 8 * x.numel() + 4 * dout.numel(),
+         lambda: lib.nrv_pool_dwconv_bwd(x.data_ptr(), w2.data_ptr(), dout.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), B, H, W, lead, C, _stream()), "nrv_pool_dwconv_bwd")
+    return dx, dw.reshape(w.shape), db
+
+
+def unfold_patches(img: Tensor, ks: int, stride: int, out: Optional[Tensor] = None) -> Tensor:
+    """nn.Unfold(ks, stride) on a contiguous NCHW image (fp32 | bf16), 1 <= stride <= ks <= 32 -> cols bf16
+    [B*Ho*Wo, pad8(ks*ks*C)], feature (c, ky, kx), zero pad columns."""
+    _dev(img, "img")
+    if img.dim() != 4 or not img.is_contiguous():
+        raise NrvError("unfold_patches: img must be a contiguous [B, C, H, W] image")
+    B, C, H, W = img.shape
+    if not 1 <= stride <= ks or H < ks or W < ks:
+        raise NrvError(f"unfold_patches: kernel {ks}, stride {stride} on a {H} x {W} image")
+    Ho, Wo = (H - ks) // stride + 1, (W - ks) // stride + 1
+    cols = _out_buffer(out, (B * Ho * Wo, pad8(ks * ks * C)), torch.bfloat16, img.device, "out")
+    _run("unfold_patches", 0.0, 4 * cols.numel(),
+         lambda: _lib.load().nrv_unfold_patches(img.data_ptr(), _dt(img, "img"), cols.data_ptr(), B, C, H, W, ks, stride, _stream()),
+         "nrv_unfold_patches")
+    return cols

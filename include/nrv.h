@@ -465,6 +465,39 @@ int nrv_head_mix_bwd(const float* dout, const float* in, const float* W, float* 
                      size_t workspace_bytes, int B, int H, int Nq, int Nk, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Re-attention on materialised matrices (added to ABI 19 without changing an existing prototype, so the version number stays;
+ * deepvit.py:47-53, 67-74, DeepViT's Attention): the attention weights of all heads are mixed by reattn_weights and then normalised
+ * by a LayerNorm over the H heads at every (query, key) position.  With S = q k^T * scale (nrv_bgemm), W = reattn_weights (fp32
+ * [H, H], indexed [h, g]), gamma / beta = reattn_norm.1.{weight, bias} (fp32 [H]):
+ *     P = softmax(S)   (deepvit.py:67-69)     M[b,g] = sum_h W[h,g] P[b,h]   (:73)
+ *     mu = mean_g M,  var = mean_g (M - mu)^2  (two-pass),  A[b,g] = (M[b,g] - mu) rsqrt(var + eps) gamma[g] + beta[g]   (:49-53, 74)
+ * and A meets v in nrv_bgemm (:78).  All matrices [B, H, Nq, Nk] contiguous; S, P, dA, dS, dP fp32; A fp32 or bf16 (a_dtype).
+ * 1 <= H <= 16, Nq >= 1, 1 <= Nk <= 1025, eps > 0, no divisibility requirement; anything else returns NRV_ERR_SHAPE before a
+ * launch.  fp32 arithmetic; mu and rstd are never stored (the backward recomputes them from P); no atomics: dW, dgamma, dbeta are
+ * sums of per-workgroup partials (workspace, H H + 2 H doubles each) added in index order by a second kernel, so reruns are
+ * bit-identical.
+ *   nrv_reattn_softmax_fwd   one pass: reads S once, writes P (kept for the backward) and A.
+ *   nrv_reattn_softmax_bwd   from dA (= dO v^T, nrv_bgemm) and P: with x^ = (M - mu) rstd and dx^ = dA gamma,
+ *                            dM[g] = rstd (dx^[g] - mean_g dx^ - x^[g] mean_g (dx^ x^)),  dP[h] = sum_g W[h,g] dM[g],
+ *                            dS = P (dP - <P, dP>_row);  dW[h,g] = sum P[b,h,i,j] dM[b,g,i,j],  dgamma[g] = sum dA x^,
+ *                            dbeta[g] = sum dA.
+ *   nrv_reattn_norm_fwd/bwd  mixing + LayerNorm alone, for robust=True (SinkhornAttention normalises rows AND columns, so it cannot
+ *                            be row-local): nrv_sinkhorn_fwd -> nrv_reattn_norm_fwd, and nrv_reattn_norm_bwd -> dP -> nrv_sinkhorn_bwd.
+ * ---------------------------------------------------------------------------------------- */
+int nrv_reattn_softmax_fwd(const float* S, const float* W, const float* gamma, const float* beta, float* P, void* A, int a_dtype,
+                           int B, int H, int Nq, int Nk, float eps, void* stream);
+size_t nrv_reattn_softmax_bwd_workspace(int B, int H, int Nq, int Nk);
+int nrv_reattn_softmax_bwd(const float* dA, const float* P, const float* W, const float* gamma, float* dS, float* dW,
+                           float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                           int B, int H, int Nq, int Nk, float eps, void* stream);
+int nrv_reattn_norm_fwd(const float* P, const float* W, const float* gamma, const float* beta, void* A, int a_dtype,
+                        int B, int H, int Nq, int Nk, float eps, void* stream);
+size_t nrv_reattn_norm_bwd_workspace(int B, int H, int Nq, int Nk);
+int nrv_reattn_norm_bwd(const float* dA, const float* P, const float* W, const float* gamma, float* dP, float* dW,
+                        float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                        int B, int H, int Nq, int Nk, float eps, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Batched small GEMM with arbitrary strides (bf16 MFMA, fp32 accumulation): for every (g1 < G1, g2 < G2)
  *   C[g1,g2][m,n] = alpha * sum_k A[g1,g2][m,k] * B[g1,g2][k,n],   element (g1, g2, row, col) of an operand at
  *   base + g1 * b1 + g2 * b2 + row * rs + col * cs  (ELEMENT strides; dtype fp32 or bf16 per operand; operands are rounded to

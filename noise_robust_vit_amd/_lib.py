@@ -147,6 +147,16 @@ SIGNATURES = {
     "nrv_head_mix_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "nrv_head_mix_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int,
                                  c_void_p]),
+    "nrv_reattn_softmax_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                       c_float, c_void_p]),
+    "nrv_reattn_softmax_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "nrv_reattn_softmax_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "nrv_reattn_norm_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                    c_void_p]),
+    "nrv_reattn_norm_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "nrv_reattn_norm_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_size_t, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "nrv_soft_split_fwd": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "nrv_soft_split_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "nrv_layernorm_pad_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

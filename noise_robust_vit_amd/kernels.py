@@ -1461,6 +1461,75 @@ def head_mix_bwd(dout: Tensor, x: Tensor, W: Tensor):
     return din, dW
 
 
+# ---- re-attention on materialised [B,H,Nq,Nk] matrices (DeepViT, deepvit.py:47-53, 67-74; include/nrv.h) -----------------
+def _ra_args(t: Tensor, W: Tensor, vecs: Tuple[Tensor, ...], eps: float, name: str) -> Tuple[int, int, int, int]:
+    B, H, Nq, Nk = _th_args(t, (W,), name)
+    for v in vecs:
+        _f32(v, "reattn_norm weight / bias")
+        if tuple(v.shape) != (H,) or not v.is_contiguous():
+            raise NrvError(f"the LayerNorm over heads takes contiguous fp32 [{H}] vectors, got {tuple(v.shape)}")
+    if not eps > 0:
+        raise NotImplementedError(f"re-attention kernels: eps must be positive, got {eps}")
+    return B, H, Nq, Nk
+
+
+def _ra_grads(H: int, dev):
+    return tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in ((H, H), (H,), (H,)))
+
+
+def reattn_softmax_fwd(S: Tensor, W: Tensor, gamma: Tensor, beta: Tensor, eps: float, a_dtype: torch.dtype = torch.bfloat16):
+    """(P fp32, A): P = softmax(S, -1), M = W-mix of P, A = LayerNorm over the heads of M at every (i, j) (deepvit.py:67-74)."""
+    B, H, Nq, Nk = _ra_args(S, W, (gamma, beta), eps, "S")
+    P = torch.empty_like(S)
+    A = torch.empty(S.shape, dtype=a_dtype, device=S.device)
+    lib = _lib.load()
+    _run("reattn_fwd", (2.0 * H + 8) * S.numel(), S.numel() * (8 + A.element_size()),
+         lambda: lib.nrv_reattn_softmax_fwd(S.data_ptr(), W.data_ptr(), gamma.data_ptr(), beta.data_ptr(), P.data_ptr(), A.data_ptr(),
+                                            _dt(A, "A"), B, H, Nq, Nk, float(eps), _stream()), "nrv_reattn_softmax_fwd")
+    return P, A
+
+
+def reattn_softmax_bwd(dA: Tensor, P: Tensor, W: Tensor, gamma: Tensor, eps: float):
+    """(dS fp32, dW [H, H], dgamma [H], dbeta [H]) of reattn_softmax_fwd from dA fp32 (= dO v^T) and the kept P."""
+    B, H, Nq, Nk = _ra_args(P, W, (gamma,), eps, "P")
+    _th_like(P, dA, "dA")
+    dS = torch.empty_like(P)
+    dW, dg, db = _ra_grads(H, P.device)
+    lib = _lib.load()
+    ws = _workspace(lib.nrv_reattn_softmax_bwd_workspace(B, H, Nq, Nk), P.device)
+    _run("reattn_bwd", (2.0 * 3 * H + 16) * P.numel(), P.numel() * 12,
+         lambda: lib.nrv_reattn_softmax_bwd(dA.data_ptr(), P.data_ptr(), W.data_ptr(), gamma.data_ptr(), dS.data_ptr(), dW.data_ptr(),
+                                            dg.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), B, H, Nq, Nk, float(eps),
+                                            _stream()), "nrv_reattn_softmax_bwd")
+    return dS, dW, dg, db
+
+
+def reattn_norm_fwd(P: Tensor, W: Tensor, gamma: Tensor, beta: Tensor, eps: float, a_dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """A = LayerNorm over the heads of the W-mix of P, alone (robust=True: P comes from sinkhorn_fwd)."""
+    B, H, Nq, Nk = _ra_args(P, W, (gamma, beta), eps, "P")
+    A = torch.empty(P.shape, dtype=a_dtype, device=P.device)
+    lib = _lib.load()
+    _run("reattn_norm_fwd", (2.0 * H + 8) * P.numel(), P.numel() * (4 + A.element_size()),
+         lambda: lib.nrv_reattn_norm_fwd(P.data_ptr(), W.data_ptr(), gamma.data_ptr(), beta.data_ptr(), A.data_ptr(), _dt(A, "A"),
+                                         B, H, Nq, Nk, float(eps), _stream()), "nrv_reattn_norm_fwd")
+    return A
+
+
+def reattn_norm_bwd(dA: Tensor, P: Tensor, W: Tensor, gamma: Tensor, eps: float):
+    """(dP fp32, dW [H, H], dgamma [H], dbeta [H]) of reattn_norm_fwd; dP goes to sinkhorn_bwd."""
+    B, H, Nq, Nk = _ra_args(P, W, (gamma,), eps, "P")
+    _th_like(P, dA, "dA")
+    dP = torch.empty_like(P)
+    dW, dg, db = _ra_grads(H, P.device)
+    lib = _lib.load()
+    ws = _workspace(lib.nrv_reattn_norm_bwd_workspace(B, H, Nq, Nk), P.device)
+    _run("reattn_norm_bwd", (2.0 * 3 * H + 16) * P.numel(), P.numel() * 12,
+         lambda: lib.nrv_reattn_norm_bwd(dA.data_ptr(), P.data_ptr(), W.data_ptr(), gamma.data_ptr(), dP.data_ptr(), dW.data_ptr(),
+                                         dg.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), B, H, Nq, Nk, float(eps),
+                                         _stream()), "nrv_reattn_norm_bwd")
+    return dP, dW, dg, db
+
+
 # ----------------------------------------------------------------------------------------------
 # tokens-to-token (t2t.py): soft split, LayerNorm over n of ld columns, wide-head streaming attention
 # ----------------------------------------------------------------------------------------------

@@ -716,6 +716,53 @@ int nrv_pool_dwconv_bwd(const float* x_f32, const float* w, const void* dout_bf1
 int nrv_unfold_patches(const void* img, int img_dtype, void* cols_bf16, int B, int C, int H, int W, int ks, int stride,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * CCT (added to ABI 19 without changing an existing prototype, so the version number stays; cct.py).
+ *
+ * ReLU + MaxPool2d on NHWC token rows (Tokenizer, cct.py:182-191).  y [B*H*W, C] is a convolution's output (y_dtype fp32 | bf16),
+ * C % 8 == 0; the pool is (pk, ps, pp) with pk in {2, 3}, 1 <= ps <= pk, pp <= pk / 2, H + 2 pp >= pk (likewise W), else
+ * NRV_ERR_SHAPE.  Ho = (H + 2 pp - pk) / ps + 1, likewise Wo.
+ *   nrv_relu_maxpool_fwd : out_f32 and / or out_bf16 [B*Ho*Wo, C] (at least one) and idx u8 [B*Ho*Wo, C]: the tap ky pk + kx of
+ *                          the FIRST maximum among the in-bounds taps, ky then kx ascending; with relu != 0 the mark 255 when
+ *                          that maximum is <= 0 (the output is then 0 and no gradient flows): autograd's rule for
+ *                          max_pool2d(relu(x)).  Values are copied: the fp32 output of an fp32 input is bit-exact, a bf16 output
+ *                          of an fp32 input is one round-to-nearest-even.
+ *   nrv_relu_maxpool_bwd : dy bf16 [B*H*W, C] from dout fp32 [B*Ho*Wo, C] and idx, in gather form: every input element sums, oy
+ *                          then ox ascending, the dout of the windows that cover it and whose idx names it; fp32 sum, one
+ *                          rounding; an element nobody selected is an exact zero.  No atomics.
+ *   Shapes first, then pointers (NRV_ERR_NULL), the dtype, then the 16-byte alignment of every pointer, all before any launch.
+ * LayerNorm with the fp32 stream on both sides (the post-norm `src = norm1(src)`, cct.py:139, and the head's norm):
+ *   nrv_layernorm_f32_fwd : x fp32 [rows, dim] -> y_f32, y_bf16 (optional copy, one rounding of y_f32), mean, rstd [rows];
+ *                           two-pass statistics, biased variance, eps inside the sqrt.
+ *   nrv_layernorm_f32_bwd : dy fp32 -> dx_f32, dx_bf16 (optional), dgamma, dbeta [dim].  A wave walks max(8, ceil(rows / 4096))
+ *                           consecutive rows; the four waves of a workgroup add their column sums in order and write one
+ *                           partial row of dgamma / dbeta into the workspace
+ *                           (nrv_layernorm_f32_bwd_workspace(rows, dim) bytes); the partial rows are summed in a fixed order.
+ *   dim % 8 == 0, 8 <= dim <= 4096, rows >= 1.
+ * Sequence pooling (cct.py:286-288): y fp32 [B*n, D], a fp32 [D] (attention_pool.weight), bias fp32 [1] (a device pointer).
+ *   nrv_seqpool_fwd : w fp32 [B, n] = softmax over a sample's n tokens of y_n . a + bias (max-subtracted), out fp32 [B, D] =
+ *                     sum_n w_n y_n, n ascending.  One workgroup per sample.
+ *   nrv_seqpool_bwd : from dout [B, D]: t_n = dout . y_n, dl_n = w_n (t_n - sum_m w_m t_m), dy_n = w_n dout + dl_n a,
+ *                     da = sum_b sum_n dl_n y_n, dbias = sum_b sum_n dl_n; per-sample partials in the workspace
+ *                     (nrv_seqpool_bwd_workspace(B, D) bytes) summed in a fixed order (lane r of 64 adds samples r, r + 64, ...,
+ *                     then the lanes in order: index order for B <= 64).
+ *   1 <= n <= 4096, D % 8 == 0, 8 <= D <= 4096, B >= 1.
+ * ---------------------------------------------------------------------------------------- */
+int nrv_relu_maxpool_fwd(const void* y, int y_dtype, int relu, float* out_f32, void* out_bf16, void* idx_u8, int B, int H, int W,
+                         int C, int pk, int ps, int pp, void* stream);
+int nrv_relu_maxpool_bwd(const float* dout, const void* idx_u8, void* dy_bf16, int B, int H, int W, int C, int pk, int ps, int pp,
+                         void* stream);
+int nrv_layernorm_f32_fwd(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_bf16, float* mean,
+                          float* rstd, int64_t rows, int dim, float eps, void* stream);
+size_t nrv_layernorm_f32_bwd_workspace(int64_t rows, int dim);
+int nrv_layernorm_f32_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                          float* dx_f32, void* dx_bf16, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                          int64_t rows, int dim, void* stream);
+int nrv_seqpool_fwd(const float* y, const float* a, const float* bias, float* w, float* out, int B, int n, int D, void* stream);
+size_t nrv_seqpool_bwd_workspace(int B, int D);
+int nrv_seqpool_bwd(const float* dout, const float* y, const float* a, const float* w, float* dy, float* da, float* dbias,
+                    void* workspace, size_t workspace_bytes, int B, int n, int D, void* stream);
+
 /* CUs the GEMM launches leave free (process-wide; default 0; returns the previous value, or a negative error code when n is
  * negative or leaves fewer than 8 CUs).  The NT GEMM is persistent (one workgroup per CU for the whole launch) and the TN
  * GEMM sizes its token splits to one round of the CUs: with a collective's kernels resident on some CUs (RCCL all-reduce

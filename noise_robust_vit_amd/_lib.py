@@ -184,6 +184,18 @@ SIGNATURES = {
     "nrv_pool_dwconv_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
                                     c_int, c_int, c_int, c_void_p]),
     "nrv_unfold_patches": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "nrv_relu_maxpool_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_void_p]),
+    "nrv_relu_maxpool_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "nrv_layernorm_f32_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float,
+                                      c_void_p]),
+    "nrv_layernorm_f32_bwd_workspace": (c_size_t, [c_int64, c_int]),
+    "nrv_layernorm_f32_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_size_t, c_int64, c_int, c_void_p]),
+    "nrv_seqpool_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "nrv_seqpool_bwd_workspace": (c_size_t, [c_int, c_int]),
+    "nrv_seqpool_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
+                                c_int, c_void_p]),
     "nrv_set_reserved_cus": (c_int, [c_int]),
     "nrv_probe": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p]),
 }

@@ -1838,3 +1838,144 @@ def unfold_patches(img: Tensor, ks: int, stride: int, out: Optional[Tensor] = No
          lambda: _lib.load().nrv_unfold_patches(img.data_ptr(), _dt(img, "img"), cols.data_ptr(), B, C, H, W, ks, stride, _stream()),
          "nrv_unfold_patches")
     return cols
+
+
+# ----------------------------------------------------------------------------------------------
+# CCT (added to ABI 19): ReLU + max pool on conv rows, LayerNorm on the fp32 stream, sequence pooling
+# ----------------------------------------------------------------------------------------------
+def maxpool_out_size(n: int, pk: int, ps: int, pp: int) -> int:
+    return (n + 2 * pp - pk) // ps + 1
+
+
+def _maxpool_geom(fn: str, B: int, H: int, W: int, pk: int, ps: int, pp: int) -> Tuple[int, int]:
+    if pk not in (2, 3) or not 1 <= ps <= pk or not 0 <= pp <= pk // 2 or min(B, H, W) < 1 or H + 2 * pp < pk or W + 2 * pp < pk:
+        raise NrvError(f"{fn}: pooling ({pk}, {ps}, {pp}) on a {H} x {W} plane: kernel 2 or 3, 1 <= stride <= kernel, padding <= kernel // 2")
+    return maxpool_out_size(H, pk, ps, pp), maxpool_out_size(W, pk, ps, pp)
+
+
+def relu_maxpool_fwd(y: Tensor, B: int, H: int, W: int, pk: int, ps: int, pp: int, relu: bool = True, want_f32: bool = True,
+                     want_bf16: bool = False, out_f32: Optional[Tensor] = None, out_bf16: Optional[Tensor] = None,
+                     idx: Optional[Tensor] = None):
+    """MaxPool2d(pk, ps, pp) of (ReLU of) the NHWC rows y [B*H*W, C] (fp32 | bf16) -> (out fp32 | None, out bf16 | None,
+    idx uint8), each [B*Ho*Wo, C] (include/nrv.h nrv_relu_maxpool_fwd)."""
+    _dev(y, "y")
+    Ho, Wo = _maxpool_geom("relu_maxpool_fwd", B, H, W, pk, ps, pp)
+    if y.dim() != 2 or not y.is_contiguous() or y.shape[0] != B * H * W or y.shape[1] % 8:
+        raise NrvError(f"relu_maxpool_fwd: y must be contiguous [{B * H * W}, C] with C % 8 == 0, got {tuple(y.shape)}")
+    C = y.shape[1]
+    if not (want_f32 or want_bf16 or out_f32 is not None or out_bf16 is not None):
+        raise NrvError("relu_maxpool_fwd: at least one of the fp32 and the bf16 output")
+    shape = (B * Ho * Wo, C)
+    o32 = _out_buffer(out_f32, shape, torch.float32, y.device, "out_f32") if (want_f32 or out_f32 is not None) else None
+    o16 = _out_buffer(out_bf16, shape, torch.bfloat16, y.device, "out_bf16") if (want_bf16 or out_bf16 is not None) else None
+    ix = _out_buffer(idx, shape, torch.uint8, y.device, "idx")
+    nb = y.numel() * y.element_size() + ix.numel() * (1 + (4 if o32 is not None else 0) + (2 if o16 is not None else 0))
+    _run("relu_maxpool_fwd", 0.0, nb,
+         lambda: _lib.load().nrv_relu_maxpool_fwd(y.data_ptr(), _dt(y, "y"), int(bool(relu)), _ptr(o32), _ptr(o16), ix.data_ptr(), B, H, W, C,
+                                                  pk, ps, pp, _stream()), "nrv_relu_maxpool_fwd")
+    return o32, o16, ix
+
+
+def relu_maxpool_bwd(dout: Tensor, idx: Tensor, B: int, H: int, W: int, pk: int, ps: int, pp: int, dy: Optional[Tensor] = None) -> Tensor:
+    """dy bf16 [B*H*W, C] from dout fp32 [B*Ho*Wo, C] and the forward's idx (include/nrv.h nrv_relu_maxpool_bwd)."""
+    _f32(dout, "dout"); _dev(idx, "idx")
+    Ho, Wo = _maxpool_geom("relu_maxpool_bwd", B, H, W, pk, ps, pp)
+    if dout.dim() != 2 or not dout.is_contiguous() or dout.shape[0] != B * Ho * Wo or dout.shape[1] % 8:
+        raise NrvError(f"relu_maxpool_bwd: dout must be contiguous [{B * Ho * Wo}, C] with C % 8 == 0, got {tuple(dout.shape)}")
+    if idx.dtype != torch.uint8 or idx.shape != dout.shape or not idx.is_contiguous():
+        raise NrvError("relu_maxpool_bwd: idx must be the forward's contiguous uint8 tensor of dout's shape")
+    C = dout.shape[1]
+    dy = _out_buffer(dy, (B * H * W, C), torch.bfloat16, dout.device, "dy")
+    _run("relu_maxpool_bwd", 0.0, dout.numel() * 5 + dy.numel() * 2,
+         lambda: _lib.load().nrv_relu_maxpool_bwd(dout.data_ptr(), idx.data_ptr(), dy.data_ptr(), B, H, W, C, pk, ps, pp, _stream()),
+         "nrv_relu_maxpool_bwd")
+    return dy
+
+
+def _lnf_args(fn: str, x: Tensor, gamma: Tensor, beta: Optional[Tensor]) -> Tuple[int, int]:
+    _f32(x, "x"); _f32(gamma, "gamma")
+    if x.dim() != 2 or not x.is_contiguous() or x.shape[0] < 1 or x.shape[1] % 8 or not 8 <= x.shape[1] <= 4096:
+        raise NrvError(f"{fn}: x must be contiguous fp32 [rows, dim] with dim % 8 == 0 and dim <= 4096, got {tuple(x.shape)}")
+    for t, n in ((gamma, "gamma"), (beta, "beta")):
+        if t is not None:
+            _f32(t, n)
+            if t.numel() != x.shape[1] or not t.is_contiguous():
+                raise NrvError(f"{fn}: {n} must hold {x.shape[1]} contiguous floats")
+    return x.shape[0], x.shape[1]
+
+
+def layernorm_f32_fwd(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, want_bf16: bool = False, y: Optional[Tensor] = None,
+                      y_bf16: Optional[Tensor] = None):
+    """nn.LayerNorm with the fp32 stream on both sides: x fp32 [rows, dim] -> (y fp32, y bf16 | None, mean, rstd)
+    (include/nrv.h nrv_layernorm_f32_fwd)."""
+    rows, dim = _lnf_args("layernorm_f32_fwd", x, gamma, beta)
+    y = _out_buffer(y, (rows, dim), torch.float32, x.device, "y")
+    y16 = _out_buffer(y_bf16, (rows, dim), torch.bfloat16, x.device, "y_bf16") if (want_bf16 or y_bf16 is not None) else None
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    _run("layernorm_f32_fwd", 0.0, rows * dim * (8 + (2 if y16 is not None else 0)),
+         lambda: _lib.load().nrv_layernorm_f32_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), _ptr(y16), mean.data_ptr(),
+                                                   rstd.data_ptr(), rows, dim, float(eps), _stream()), "nrv_layernorm_f32_fwd")
+    return y, y16, mean, rstd
+
+
+def layernorm_f32_bwd(dy: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: Tensor, want_bf16: bool = False,
+                      dx: Optional[Tensor] = None, dx_bf16: Optional[Tensor] = None):
+    """(dx fp32, dx bf16 | None, dgamma, dbeta) from an fp32 dy (include/nrv.h nrv_layernorm_f32_bwd)."""
+    rows, dim = _lnf_args("layernorm_f32_bwd", x, gamma, None)
+    _f32(dy, "dy"); _f32(mean, "mean"); _f32(rstd, "rstd")
+    if dy.shape != x.shape or not dy.is_contiguous() or mean.numel() != rows or rstd.numel() != rows:
+        raise NrvError("layernorm_f32_bwd: dy must match x, mean and rstd hold one value per row")
+    dx = _out_buffer(dx, (rows, dim), torch.float32, x.device, "dx")
+    dx16 = _out_buffer(dx_bf16, (rows, dim), torch.bfloat16, x.device, "dx_bf16") if (want_bf16 or dx_bf16 is not None) else None
+    dg = torch.empty(dim, dtype=torch.float32, device=x.device)
+    db = torch.empty(dim, dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    ws = _workspace(lib.nrv_layernorm_f32_bwd_workspace(rows, dim), x.device)
+    _run("layernorm_f32_bwd", 0.0, rows * dim * (12 + (2 if dx16 is not None else 0)),
+         lambda: lib.nrv_layernorm_f32_bwd(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
+                                           _ptr(dx16), dg.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), rows, dim, _stream()),
+         "nrv_layernorm_f32_bwd")
+    return dx, dx16, dg, db
+
+
+def _seqpool_args(fn: str, y: Tensor, a: Tensor, B: int, n: int) -> int:
+    _f32(y, "y"); _f32(a, "a")
+    if y.dim() != 2 or not y.is_contiguous() or B < 1 or not 1 <= n <= 4096 or y.shape[0] != B * n or y.shape[1] % 8 or not 8 <= y.shape[1] <= 4096:
+        raise NrvError(f"{fn}: y must be contiguous fp32 [B*n, D] with 1 <= n <= 4096, D % 8 == 0 and D <= 4096, got {tuple(y.shape)} "
+                       f"for B {B}, n {n}")
+    if a.numel() != y.shape[1] or not a.is_contiguous():
+        raise NrvError(f"{fn}: a must hold {y.shape[1]} contiguous floats")
+    return y.shape[1]
+
+
+def seqpool_fwd(y: Tensor, a: Tensor, bias: Tensor, B: int, n: int, w: Optional[Tensor] = None, out: Optional[Tensor] = None):
+    """(w fp32 [B, n], out fp32 [B, D]): w = softmax_n(y a + bias), out = sum_n w_n y_n (include/nrv.h nrv_seqpool_fwd);
+    bias is a one-element device tensor."""
+    D = _seqpool_args("seqpool_fwd", y, a, B, n)
+    _f32(bias, "bias")
+    if bias.numel() != 1:
+        raise NrvError("seqpool_fwd: bias holds one float")
+    w = _out_buffer(w, (B, n), torch.float32, y.device, "w")
+    out = _out_buffer(out, (B, D), torch.float32, y.device, "out")
+    _run("seqpool_fwd", 4.0 * y.numel(), 8 * y.numel(),
+         lambda: _lib.load().nrv_seqpool_fwd(y.data_ptr(), a.data_ptr(), bias.data_ptr(), w.data_ptr(), out.data_ptr(), B, n, D, _stream()),
+         "nrv_seqpool_fwd")
+    return w, out
+
+
+def seqpool_bwd(dout: Tensor, y: Tensor, a: Tensor, w: Tensor, B: int, n: int, dy: Optional[Tensor] = None):
+    """(dy fp32 like y, da fp32 [D], dbias fp32 [1]) from dout fp32 [B, D] (include/nrv.h nrv_seqpool_bwd)."""
+    D = _seqpool_args("seqpool_bwd", y, a, B, n)
+    _f32(dout, "dout"); _f32(w, "w")
+    if tuple(dout.shape) != (B, D) or not dout.is_contiguous() or tuple(w.shape) != (B, n) or not w.is_contiguous():
+        raise NrvError(f"seqpool_bwd: dout must be contiguous [{B}, {D}] and w [{B}, {n}]")
+    dy = _out_buffer(dy, y.shape, torch.float32, y.device, "dy")
+    da = torch.empty(D, dtype=torch.float32, device=y.device)
+    db = torch.empty(1, dtype=torch.float32, device=y.device)
+    lib = _lib.load()
+    ws = _workspace(lib.nrv_seqpool_bwd_workspace(B, D), y.device)
+    _run("seqpool_bwd", 8.0 * y.numel(), 12 * y.numel(),
+         lambda: lib.nrv_seqpool_bwd(dout.data_ptr(), y.data_ptr(), a.data_ptr(), w.data_ptr(), dy.data_ptr(), da.data_ptr(), db.data_ptr(),
+                                     ws.data_ptr(), ws.numel(), B, n, D, _stream()), "nrv_seqpool_bwd")
+    return dy, da, db

@@ -1171,9 +1171,50 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_tn_kernel(const GemmTNParam
 // swizzled by the row), B half image = [64 token rows][the 32 columns of half h of the four wave columns]; both are read
 // with ds_read_b64_tr_b16.  Host: no row remap, every split has at least three K-steps.
 // ---------------------------------------------------------------------------------------------
+// The bias-gradient chain of one phase of tn8_segment: c += ones . a[sel][0], then c += ones . a[sel][1]; sel < 0: nothing
+// (sel is wave-uniform).  ONE asm statement that branches inside, so that the compiler sees straight-line code that updates
+// c in place.  Written with the builtin under an `if`, the sum came out of the branch in other registers than it went in
+// and was copied back with VALU moves; a VALU read of an MFMA result waits for every MFMA queued before it, so the wave
+// reached the phase's closing barrier a whole quadrant late (a launch with a bias gradient ran 12 - 14 % longer for 2 %
+// more MFMAs).  The s_nop and the scalar compares give the two wait states between a VALU write of an operand (the ones
+// vector is rematerialised in front) and the MFMA that reads it, which the compiler cannot count for instructions it does
+// not see; the second link of the chain reads the first one's registers as they are.
+__device__ __forceinline__ void bias_chain(f32x4_t& c, bf16x8_t ones, const bf16x8_t (&a)[4][2], int sel) {
+    asm volatile(
+        "s_nop 1\n\t"
+        "s_cmp_lt_i32 %[s], 0\n\t"
+        "s_cbranch_scc1 .Lbias_end_%=\n\t"
+        "s_cmp_lg_u32 %[s], 0\n\t"
+        "s_cbranch_scc1 .Lbias_1_%=\n\t"
+        "v_mfma_f32_16x16x32_bf16 %[c], %[o], %[a00], %[c]\n\t"
+        "v_mfma_f32_16x16x32_bf16 %[c], %[o], %[a01], %[c]\n\t"
+        "s_branch .Lbias_end_%=\n"
+        ".Lbias_1_%=:\n\t"
+        "s_cmp_lg_u32 %[s], 1\n\t"
+        "s_cbranch_scc1 .Lbias_2_%=\n\t"
+        "v_mfma_f32_16x16x32_bf16 %[c], %[o], %[a10], %[c]\n\t"
+        "v_mfma_f32_16x16x32_bf16 %[c], %[o], %[a11], %[c]\n\t"
+        "s_branch .Lbias_end_%=\n"
+        ".Lbias_2_%=:\n\t"
+        "s_cmp_lg_u32 %[s], 2\n\t"
+        "s_cbranch_scc1 .Lbias_3_%=\n\t"
+        "v_mfma_f32_16x16x32_bf16 %[c], %[o], %[a20], %[c]\n\t"
+        "v_mfma_f32_16x16x32_bf16 %[c], %[o], %[a21], %[c]\n\t"
+        "s_branch .Lbias_end_%=\n"
+        ".Lbias_3_%=:\n\t"
+        "v_mfma_f32_16x16x32_bf16 %[c], %[o], %[a30], %[c]\n\t"
+        "v_mfma_f32_16x16x32_bf16 %[c], %[o], %[a31], %[c]\n"
+        ".Lbias_end_%=:"
+        : [c] "+v"(c)
+        : [o] "v"(ones), [a00] "v"(a[0][0]), [a01] "v"(a[0][1]), [a10] "v"(a[1][0]), [a11] "v"(a[1][1]),
+          [a20] "v"(a[2][0]), [a21] "v"(a[2][1]), [a30] "v"(a[3][0]), [a31] "v"(a[3][1]), [s] "s"(sel)
+        : "scc");
+}
+
 // one unit of TN work: the 256 x 256 output tile (m0, n0) of C = A^T B over the token rows [t_begin, t_begin + trem), nk K-steps
 // (the last one may be partial), written as an fp32 tile to `out` (leading dimension out_ld: a slab of the whole matrix, or a
-// dense tile slot) and, with bias_out, the column sums of A of those rows to bias_out[0 .. 255] (first column tile only)
+// dense tile slot) and, with bias_out, the column sums of A of those rows to the 16-float ranges of bias_out[0 .. 255] that
+// belong to the unit's blocks (bias_mod / bias_rem: the 16 blocks of a row tile are dealt out over its column tiles)
 struct TnSeg {
     const bf16_t* A;
     const bf16_t* B;
@@ -1183,6 +1224,7 @@ struct TnSeg {
     float* out;                      // element (m0, n0) of the destination
     long long out_ld;
     float* bias_out;                 // element m0 of the destination, or nullptr
+    int bias_mod, bias_rem;          // with bias_out: this unit sums the 16-column blocks b of the row tile with b % bias_mod == bias_rem
 };
 
 template <typename C>
@@ -1285,13 +1327,33 @@ __device__ __forceinline__ void tn8_segment(const TnSeg& sg, char* smem) {
         for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     bf16x8_t a[MH][2], bs[2][2][2];            // as in gemm_nt8_kernel: bs[q] / bs[q ^ 1] = B0 / B1 of a K-step of parity q
 
-    // fused bias gradient db[m] = sum_t A[t, m] = (ones . A) on the MFMA, first column tile only; wave column wc takes the row
-    // blocks 2 wc, 2 wc + 1 of its wave row: half wc >> 1, fragments (wc & 1) * MH / 2 + {0, 1}
+    // fused bias gradient db[m] = sum_t A[t, m] = (ones . A) on the MFMA.  Row block b = 8 wr + 4 h + ml of the row tile (16
+    // columns of A: fragment a[ml] of half h, held by all four waves of wave row wr in phases 2 h and 2 h + 1) belongs to the
+    // unit with b % bias_mod == bias_rem.  The unit's blocks of (wr, h) go one each to different waves of the wave row, in
+    // phase 2 h: the k-th to wave column k in wave row 0 and 3 - k in wave row 1, so that the two wave rows load different
+    // SIMDs first.  A block is one accumulator chain (two MFMAs per K-step, ks = 0 then 1) whoever runs it: a wave carries
+    // at most one block per phase (two of the quadrant's 16 + 2 MFMAs), where the first column tile used to add four to four
+    // of its waves and every launch waited for those workgroups.
     static_assert(MH == 4, "bias-gradient block assignment");
     const bool do_bias = sg.bias_out != nullptr;
+    int bml[2] = {-1, -1};                                     // fragment of half h this wave sums, or -1 (wave-uniform)
+    if (do_bias) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            int k = 0;
+#pragma unroll
+            for (int ml = 0; ml < MH; ++ml) {
+                if ((8 * wr + 4 * h + ml) % sg.bias_mod == sg.bias_rem) {
+                    if ((wr ? 3 - k : k) == wc) bml[h] = ml;
+                    ++k;
+                }
+            }
+            bml[h] = __builtin_amdgcn_readfirstlane(bml[h]);
+        }
+    }
     const u32x4_t ones_u = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
     bf16x8_t ones = __builtin_bit_cast(bf16x8_t, ones_u);
-    f32x4_t accb[2];
+    f32x4_t accb[2];                                           // accb[h]: the block of half h
     accb[0] = accb[1] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
@@ -1351,19 +1413,8 @@ __device__ __forceinline__ void tn8_segment(const TnSeg& sg, char* smem) {
                         acc[mh + ml][nh + nl] = mfma16(bs[bq][nl][ks], a[ml][ks], acc[mh + ml][nh + nl]);
             NRV_WACC(4 * P + 1);                                  // section 1: the quadrant's 16 MFMAs issued
             if constexpr (P == 0 || P == 2) {
-                if (do_bias && (wc >> 1) == P / 2) {              // uniform
-                    if (wc & 1) {
-#pragma unroll
-                        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                            for (int j = 0; j < 2; ++j) accb[j] = mfma16(ones, a[2 + j][ks], accb[j]);
-                    } else {
-#pragma unroll
-                        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                            for (int j = 0; j < 2; ++j) accb[j] = mfma16(ones, a[j][ks], accb[j]);
-                    }
-                }
+                constexpr int h = P / 2;
+                bias_chain(accb[h], ones, a, bml[h]);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -1417,11 +1468,11 @@ __device__ __forceinline__ void tn8_segment(const TnSeg& sg, char* smem) {
     if (NRV_TUNE_STAGGER(wr == 0)) __builtin_amdgcn_s_barrier();
     NRV_WACC_FLUSH(8, wave, lane);
 
-    if (do_bias && lane < 16) {
+    if (lane < 16) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int ml = wr * (C::MI * 16) + (2 * wc + j) * 16 + lane;
-            if (m0 + ml < M) sg.bias_out[ml] = accb[j][0];
+        for (int h = 0; h < 2; ++h) {
+            const int ml = wr * (C::MI * 16) + (4 * h + bml[h]) * 16 + lane;
+            if (bml[h] >= 0 && m0 + ml < M) sg.bias_out[ml] = accb[h][0];
         }
     }
     // the destination is addressed relative to the tile: rows / columns beyond the matrix are dropped by the range check
@@ -1451,7 +1502,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_tn8_kernel(const GemmTNP
     sg.trem = t_end - sg.t_begin;
     sg.out = reinterpret_cast<float*>(p.e.C) + (long long)split * p.slab_stride + (long long)sg.m0 * p.e.ldc + sg.n0;
     sg.out_ld = p.e.ldc;
-    sg.bias_out = (p.bias_ws != nullptr && tn == 0) ? p.bias_ws + (long long)split * p.e.M + sg.m0 : nullptr;
+    // every column tile of a row tile writes its own blocks of the split's bias row: disjoint 16-float ranges, one writer each
+    sg.bias_out = p.bias_ws != nullptr ? p.bias_ws + (long long)split * p.e.M + sg.m0 : nullptr;
+    sg.bias_mod = p.tiles_n; sg.bias_rem = tn;
     tn8_segment<C>(sg, smem);
 }
 
@@ -1523,7 +1576,10 @@ __device__ __forceinline__ void tng_run(const GemmTNGParams& p, int tile, int k0
     sg.trem = t_end - sg.t_begin;
     sg.out = p.slots + (long long)slot * (C::TBM * C::TBN);
     sg.out_ld = C::TBN;
+    // the column tiles of a row tile are cut into segments at different K positions here, so a bias slot stays the whole row
+    // of the first column tile's segment: all 16 blocks, one per wave and phase
     sg.bias_out = (q.dbias != nullptr && tn == 0) ? p.bias_slots + (long long)slot * C::TBM : nullptr;
+    sg.bias_mod = 1; sg.bias_rem = 0;
     tn8_segment<C>(sg, smem);
 }
 

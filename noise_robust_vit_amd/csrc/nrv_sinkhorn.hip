@@ -834,9 +834,10 @@ int launch_sk_bwd(const SinkParams& p, hipStream_t s) {
     return 0;
 }
 
-int sk_check(int B, int N, int H, int dh) {
+int sk_check(int B, int N, int H, int dh, float scale) {
     if (B <= 0 || N <= 0 || H <= 0) return NRV_ERR_SHAPE;
     if (dh != DH || N > 256) return NRV_ERR_SHAPE;
+    if (!(scale > 0.f)) return NRV_ERR_SHAPE;       // softmax_tile scales the row maximum of the RAW scores: right for scale > 0 only (NaN is refused too)
     return 0;
 }
 
@@ -857,7 +858,7 @@ int sk_check(int B, int N, int H, int dh) {
 extern "C" int nrv_attn_sinkhorn_fwd(const void* qkv_bf16, void* out_bf16, float* lse, float* scalings,
                                      int B, int N, int H, int dh, float scale, void* stream) {
     if (!qkv_bf16 || !out_bf16 || !lse || !scalings) return NRV_ERR_NULL;
-    if (int e = sk_check(B, N, H, dh)) return e;
+    if (int e = sk_check(B, N, H, dh, scale)) return e;
     if (!nrv_aligned16(qkv_bf16) || !nrv_aligned16(out_bf16)) return NRV_ERR_ALIGN;
     SinkParams p{};
     p.qkv = static_cast<const bf16_t*>(qkv_bf16);
@@ -871,7 +872,7 @@ extern "C" int nrv_attn_sinkhorn_fwd(const void* qkv_bf16, void* out_bf16, float
 extern "C" int nrv_attn_sinkhorn_bwd(const void* qkv_bf16, const void* dout_bf16, const float* lse, const float* scalings,
                                      void* dqkv_bf16, int B, int N, int H, int dh, float scale, void* stream) {
     if (!qkv_bf16 || !dout_bf16 || !lse || !scalings || !dqkv_bf16) return NRV_ERR_NULL;
-    if (int e = sk_check(B, N, H, dh)) return e;
+    if (int e = sk_check(B, N, H, dh, scale)) return e;
     if (!nrv_aligned16(qkv_bf16) || !nrv_aligned16(dout_bf16) || !nrv_aligned16(dqkv_bf16)) return NRV_ERR_ALIGN;
     SinkParams p{};
     p.qkv = static_cast<const bf16_t*>(qkv_bf16);

@@ -20,8 +20,14 @@ Not in the table:
   * nrv_pcn.hip's elementwise kernels (dw_bwd_da, se_apply, ls_add, dgelu_rows): PCN_GRID_CAP = 65535 x 8 workgroups of 256
     threads x 4 elements wrap above 5.4e8 elements, which neither a test of a few seconds nor the workload reaches.
   * bn_bwd_apply_kernel (8192 x 256 elements, wrapped by test_bn_rows_gpu.py's 12544 x 640), nrv_sumsq_f32 (1024 x 256 x 4,
-    wrapped by test_optim_gpu.py), the talking-heads kernels, and the persistent GEMM / attention / Sinkhorn walks, which
-    their own tests already run over several passes.
+    wrapped by test_optim_gpu.py), the talking-heads kernels, and the persistent GEMM / attention walks, which their own
+    tests already run over several passes.
+  * the persistent walk of the fused Sinkhorn pair (nrv_sinkhorn.hip: one workgroup per CU, the K / V image slots alternating
+    with `it & 1`).  Its older many-head tests use 270 and 276 heads on 256 CUs, two passes at the most, so no slot was ever
+    reused.  The walk cases of tests/sinkhorn_edges_ref.py (WALK_SPECS, run by test_sinkhorn_edges_gpu.py) hold it to the
+    standard of this table: 3 cus + 7 heads at N = 17 and 33, as (heads, 1) and as (ceil(heads / 5), 5), and
+    ceil(2.25 cus) + 3 heads at N = 129, 197 and (forward only) 225, with cus read from the device and every head checked
+    per row; test_sinkhorn_edges_ref_host.py asserts the pass counts for several CU counts.
 """
 from __future__ import annotations
 

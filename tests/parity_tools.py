@@ -10,10 +10,37 @@ are produced, all max-norm relative to the oracle stream at that stage:
 `iso_emu` is the number that localises: it removes accumulation, so a rounding point the emulation misses (or a wrong
 kernel) shows up as one stage with a large isolated error, while pure rounding-boundary flips give the same small
 isolated error at every stage.
+
+`_Out` is the guarded, NaN-pre-filled output buffer of the per-row edge tests that call the C ABI with buffers they own
+(test_attn_edges_gpu.py, test_sinkhorn_edges_gpu.py).
 """
 from __future__ import annotations
 
 import torch
+
+
+bf = torch.bfloat16
+GUARD = 256                                  # elements on either side of an output
+PATTERN = {bf: (torch.int16, 0x7FC1), torch.float32: (torch.int32, 0x7FC00001)}     # NaNs that are not torch's nor any arithmetic's
+
+
+class _Out:
+    """A NaN-filled output of `numel` elements between two guard blocks."""
+    def __init__(self, numel, dtype, dev):
+        it, pat = PATTERN[dtype]
+        self.raw = torch.full((numel + 2 * GUARD,), pat, dtype=it, device=dev)
+        self.t = self.raw.view(dtype)[GUARD:GUARD + numel]
+        self.t.fill_(float("nan"))
+        self.pat = pat
+
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def done(self, what, written=True):
+        assert bool((self.raw[:GUARD] == self.pat).all()) and bool((self.raw[-GUARD:] == self.pat).all()), f"{what}: a guard element was written"
+        if written:
+            assert not bool(torch.isnan(self.t).any()), f"{what}: an output element was never written"
+        return self.t
 
 
 def _rel(a: torch.Tensor, b: torch.Tensor) -> float:

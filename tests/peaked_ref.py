@@ -91,30 +91,32 @@ def heads(t: torch.Tensor, B: int, N: int, H: int, dh: int) -> torch.Tensor:
 def attention_reference(qkv: torch.Tensor, dout: Optional[torch.Tensor], B: int, N: int, H: int, dh: int, scale: float, *,
                         iters: int = 3, dtype: torch.dtype = torch.float64, emulate_bf16: bool = False,
                         bias: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, pscale: float = 1.0,
-                        drop_keys: Sequence[int] = ()) -> dict:
+                        drop_keys: Sequence[int] = (), device=None) -> dict:
     """o [B,H,N,dh], P [B,H,N,N] (before the keep mask), lse [B,H,N] and -- with `dout` [B*N, H*dh] -- dq, dk, dv [B,H,N,dh], all in
     `dtype`, by autograd through the definition.  `iters` = 0 is softmax attention.  `emulate_bf16`: P (after the keep mask), dS
     and o / dq / dk / dv are rounded to bf16 inside the evaluation (straight-through): the kernels' rounding points.
     `drop_keys`: the definition evaluated WITHOUT those keys (their score columns and value rows are removed; their dk / dv rows are
-    zero) -- what a kernel must return for a key whose column underflows completely, where the definition itself is 0 / 0."""
-    x = qkv.detach().cpu().to(dtype).requires_grad_(dout is not None)
+    zero) -- what a kernel must return for a key whose column underflows completely, where the definition itself is 0 / 0.
+    `device`: where the evaluation runs and the results stay (default: the CPU) -- the same arithmetic in the same `dtype`."""
+    device = torch.device("cpu") if device is None else device
+    x = qkv.detach().to(device).to(dtype).requires_grad_(dout is not None)
     q, k, v = heads(x, B, N, H, dh)
     S = (q @ k.transpose(-1, -2)) * scale
     if bias is not None:
-        S = S + bias.detach().cpu().to(dtype)
+        S = S + bias.detach().to(device).to(dtype)
     if drop_keys:
         kept = [j for j in range(N) if j not in set(drop_keys)]
         S, v = S[..., kept], v[..., kept, :]
     if emulate_bf16:
         S = _RoundGrad.apply(S)
     P = sinkhorn_definition(S, iters)
-    Pv = P if keep is None else P * (keep.detach().cpu() != 0).to(dtype) * pscale
+    Pv = P if keep is None else P * (keep.detach().to(device) != 0).to(dtype) * pscale
     if emulate_bf16:
         Pv = _round_st(Pv)
     o = Pv @ v
     res = {"o": o.detach(), "P": P.detach(), "lse": torch.logsumexp(S.detach(), dim=-1)}
     if dout is not None:
-        o.backward(heads(dout.detach().cpu().to(dtype), B, N, H, dh)[0])
+        o.backward(heads(dout.detach().to(device).to(dtype), B, N, H, dh)[0])
         res["dq"], res["dk"], res["dv"] = heads(x.grad, B, N, H, dh)
     if emulate_bf16:
         for name in ("o", "dq", "dk", "dv"):

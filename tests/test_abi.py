@@ -111,6 +111,10 @@ def test_loader_sets_prototypes_and_reports_errors(lib_path):
     assert lib.nrv_gather_rows_f32(16, 16, 16, 4, 0, 64, None) == -2                            # ABI 11: the source-row count is required
     assert lib.nrv_bgemm(None, 1, 1, 1, 0, 0, 16, 1, 1, 1, 0, 0, 16, 0, 1, 1, 0, 0, 1, 1, 8, 8, 8, ctypes.c_float(1.0), None) == -1
     assert lib.nrv_attn_sinkhorn_fwd(1, 1, 1, 1, 1, 300, 1, 64, ctypes.c_float(0.125), None) == -2   # Sinkhorn: N <= 256 only
+    for bad in (0.0, -0.125, float("nan")):          # ... and scale > 0 only: the forward scales the maximum of the raw scores
+        assert lib.nrv_attn_sinkhorn_fwd(1, 1, 1, 1, 1, 197, 1, 64, ctypes.c_float(bad), None) == -2
+        assert lib.nrv_attn_sinkhorn_bwd(1, 1, 1, 1, 1, 1, 197, 1, 64, ctypes.c_float(bad), None) == -2
+    assert lib.nrv_attn_sinkhorn_fwd(1, 1, 1, 1, 1, 197, 1, 64, ctypes.c_float(0.125), None) == -5   # a good scale: on to the alignment check
     assert lib.nrv_layernorm_fwd(16, 0, 16, 16, 16, 16, 16, 4, 12, ctypes.c_float(1e-5), None) == -2   # dim % 8
     assert b"shape" in lib.nrv_error_string(-2)
     with pytest.raises(_lib.NrvError):

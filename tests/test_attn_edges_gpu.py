@@ -25,30 +25,10 @@ import torch
 import attn_edges_ref as R
 from noise_robust_vit_amd import _lib
 from noise_robust_vit_amd import kernels as K
+from parity_tools import _Out                 # the guarded, NaN-pre-filled output (shared with test_sinkhorn_edges_gpu.py)
 
 pytestmark = pytest.mark.gpu
 bf = torch.bfloat16
-GUARD = 256                                  # elements on either side of an output
-PATTERN = {bf: (torch.int16, 0x7FC1), torch.float32: (torch.int32, 0x7FC00001)}     # NaNs that are not torch's nor any arithmetic's
-
-
-class _Out:
-    """A NaN-filled output of `numel` elements between two guard blocks."""
-    def __init__(self, numel, dtype, dev):
-        it, pat = PATTERN[dtype]
-        self.raw = torch.full((numel + 2 * GUARD,), pat, dtype=it, device=dev)
-        self.t = self.raw.view(dtype)[GUARD:GUARD + numel]
-        self.t.fill_(float("nan"))
-        self.pat = pat
-
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def done(self, what, written=True):
-        assert bool((self.raw[:GUARD] == self.pat).all()) and bool((self.raw[-GUARD:] == self.pat).all()), f"{what}: a guard element was written"
-        if written:
-            assert not bool(torch.isnan(self.t).any()), f"{what}: an output element was never written"
-        return self.t
 
 
 def _st():

@@ -213,6 +213,37 @@ int nrv_attn_bwd(const void* qkv_bf16, const void* out_bf16, const void* dout_bf
 int nrv_attn_probs(const void* qkv_bf16, const float* lse, float* probs,
                    int B, int N, int H, int dh, float scale, int layout, void* stream);
 
+/* Attention-weight dropout inside nrv_attn_fwd / _bwd's kernels (vit.py:108: F.dropout(softmax(...), p), with the mask drawn
+ * here and regenerated in the backward; nothing of size N^2 is written).  Entry points added under ABI 19.
+ *   P = softmax(scale q k^T);  Pd = P o keep / (1 - p_eff);  out = Pd v.  lse, the row maximum and the row sum are those of the
+ *   undropped row (bit-identical to nrv_attn_fwd's); P o keep is rounded to bf16 as the MFMA operand and 1 / (l (1 - p_eff)) is
+ *   applied in fp32 at the end.  Backward with M = keep / (1 - p_eff): dV = (P o M)^T dO, dS = P o (M o (dO v^T) - delta),
+ *   delta = rowsum(dO o out) as without dropout.  A query whose keys are all dropped has out and dq exactly zero.
+ *   Shapes and pointers as nrv_attn_fwd / _bwd with layout 0 (row-major only).  seed_dev: 64 bits in DEVICE memory (8-byte
+ *   aligned), read by the kernels when they run, so a captured graph draws a new mask per replay.
+ *
+ *   Decisions.  T = nrv_attn_drop_threshold(p) = floor(p * 2^16 + 1/2) (p taken as the float it is passed as), p_eff = T / 2^16;
+ *   T = 0 runs the plain kernels (bit-identical results).  keep(seed, g, q, k) for g = b * H + h is a stateless function of
+ *   exactly these four values; all arithmetic is on uint32, wrapping:
+ *     fmix(h):  h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16          (murmur3's finaliser)
+ *     head(c) = fmix(fmix(fmix(seed_lo + c) ^ seed_hi) + g)           seed_lo / seed_hi = the low / high 32 bits of the seed
+ *     row keys of query q:  a0 = fmix(head(0x9E3779B9) ^ q),  a1 = fmix(head(0x7F4A7C15) ^ q)
+ *     word of (q, key pair kp = k >> 1):
+ *         t = a0 + kp * 0x9E3779B9;  t ^= t >> 16;  t *= 0x85EBCA6B;  t ^= a1;  t ^= t >> 13;  t *= 0xC2B2AE35;  t ^= t >> 16
+ *     r(q, k) = bits 16 (k & 1) .. 16 (k & 1) + 15 of the word;   keep  <=>  r >= T
+ *   The row keys cost eight multiplies once per (query, kernel); a word costs two multiplies and decides two keys of one
+ *   query.  The query-owner kernels (forward, dQ) draw two words per four keys of a lane; the key-owner kernels (dK / dV), whose
+ *   lanes hold four queries of one key, read the row keys from LDS and draw four words per four elements.
+ *   nrv_attn_drop_mask writes the decisions themselves, uint8 [B, H, N, N] (1 = kept), for tests and for the composed path.
+ *   Errors before any launch: NRV_ERR_NULL, NRV_ERR_SHAPE (shape; p < 0, p >= 1, NaN, or a T of 65536), NRV_ERR_ALIGN. */
+int nrv_attn_drop_threshold(float p);   /* T in [0, 65535], or NRV_ERR_SHAPE */
+int nrv_attn_drop_fwd(const void* qkv_bf16, void* out_bf16, float* lse, const uint64_t* seed_dev, float p,
+                      int B, int N, int H, int dh, float scale, void* stream);
+int nrv_attn_drop_bwd(const void* qkv_bf16, const void* out_bf16, const void* dout_bf16, const float* lse,
+                      void* dqkv_bf16, float* delta_ws, const uint64_t* seed_dev, float p,
+                      int B, int N, int H, int dh, float scale, void* stream);
+int nrv_attn_drop_mask(const uint64_t* seed_dev, float p, unsigned char* keep, int B, int H, int N, void* stream);
+
 /* Attention with memory keys and a score mask (ABI 14; learnable_memory_vit.py:64-86, the Adapter's attention).
  *   Queries: the Nq token rows of qkv bf16 [B, Nq, 3*H*dh] (same layout as nrv_attn_fwd).  Keys / values: those Nq rows
  *   followed by M memory rows, Nk = Nq + M; memory row r of sample b is row b*mem_bstride + r of mem_kv bf16 [*, 2*H*dh]

@@ -73,6 +73,11 @@ SIGNATURES = {
     "nrv_attn_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "nrv_attn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "nrv_attn_drop_threshold": (c_int, [c_float]),
+    "nrv_attn_drop_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "nrv_attn_drop_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                  c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "nrv_attn_drop_mask": (c_int, [c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     "nrv_attn_probs": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "nrv_attn_mem_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64,
                                  c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),

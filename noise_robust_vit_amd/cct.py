@@ -10,7 +10,10 @@ cct.py, so seeded models and reference checkpoints are interchangeable.  `sinuso
 
 Added keywords, all defaulting to the reference's behaviour: `robust=False` on CCT, TransformerClassifier,
 TransformerEncoderLayer and Attention selects SinkhornAttention's normalisation (utils.py:1025-1037) instead of softmax;
-`attention_dropout=0.1` on CCT.  The reference's CCT hard-wires attention_dropout=0.1, seq_pool=True and dropout_rate=0. in its
+`attention_dropout=0.1` on CCT; `fused_attention_dropout=False` on the same four classes runs the dropout on the attention
+weights inside the fused softmax kernels (kernels.attn_drop_fwd: the mask is a function of a 64-bit seed, regenerated in the
+backward, nothing of size n^2 is written) instead of on the composed path's materialised matrix -- robust=True stays
+composed.  The reference's CCT hard-wires attention_dropout=0.1, seq_pool=True and dropout_rate=0. in its
 call of TransformerClassifier, so passing seq_pool or dropout_rate to CCT raises TypeError (here too), and it passes a
 `stochastic_depth=0.1` that the classifier's **kwargs swallows: the knob that works is `stochastic_depth_rate` (default 0.1).
 That quirk is kept.
@@ -21,7 +24,7 @@ The step on the fp32 stream x [B*n, D]:
                  nrv_relu_maxpool_fwd (fp32 token stream from the last layer, bf16 rows for the next conv, uint8 argmax kept)
     + positional table, class token (torch: B*n*D elements of plumbing)
     BlockFn      x1 = x + dp(attn(LN_pre x))     encoder.attn_half_fwd (fused softmax / Sinkhorn; weight dropout in training:
-                                                 the composed path), per-sample drop path through nrv_sd_add_f32
+                                                 the composed path, or the fused kernels with fused_attention_dropout), per-sample drop path through nrv_sd_add_f32
                  y  = LN_1(x1)                   nrv_layernorm_f32_fwd: the LayerNorm's OUTPUT is the fp32 stream (post-norm)
                  out = y + dp(linear2(gelu(linear1 y)))
     head         nrv_layernorm_f32_fwd -> nrv_seqpool_fwd (or row 0 with seq_pool=False) -> fc (torch, B rows)
@@ -119,7 +122,7 @@ def sinusoidal_embedding(n_channels, dim):
 class Attention(nn.Module):
     """cct.py:84-111.  Holds the parameters; the attention runs inside its TransformerEncoderLayer's schedule."""
 
-    def __init__(self, dim, num_heads=8, attention_dropout=0.1, projection_dropout=0.1, robust=False):
+    def __init__(self, dim, num_heads=8, attention_dropout=0.1, projection_dropout=0.1, robust=False, fused_attention_dropout=False):
         super().__init__()
         self.heads = num_heads
         head_dim = dim // self.heads
@@ -128,6 +131,9 @@ class Attention(nn.Module):
                                       f"{_FUSED_DH} (the attention kernels)")
         self.scale = head_dim ** -0.5
         self.robust = bool(robust)
+        # dropout on the attention weights inside the fused softmax kernels (kernels.attn_drop_fwd) instead of on a materialised
+        # [B, H, n, n] matrix; robust=True keeps the composed path
+        self.fused_attention_dropout = bool(fused_attention_dropout)
         self.qkv = nn.Linear(dim, dim * 3, bias=False)
         self.attn_drop = nn.Dropout(attention_dropout)
         self.proj = nn.Linear(dim, dim)
@@ -237,13 +243,14 @@ class BlockFn(torch.autograd.Function):
 class TransformerEncoderLayer(nn.Module):
     """cct.py:114-142.  forward(src [B, n, d_model]) on the HIP device."""
 
-    def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1, attention_dropout=0.1, drop_path_rate=0.1, robust=False):
+    def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1, attention_dropout=0.1, drop_path_rate=0.1, robust=False,
+                 fused_attention_dropout=False):
         super().__init__()
         if dim_feedforward % 8 or dim_feedforward < 8:
             raise NotImplementedError(f"dim_feedforward {dim_feedforward}: the kernels take multiples of 8")
         self.pre_norm = nn.LayerNorm(d_model)
         self.self_attn = Attention(dim=d_model, num_heads=nhead, attention_dropout=attention_dropout, projection_dropout=dropout,
-                                   robust=robust)
+                                   robust=robust, fused_attention_dropout=fused_attention_dropout)
         self.linear1 = nn.Linear(d_model, dim_feedforward)
         self.dropout1 = nn.Dropout(dropout)
         self.norm1 = nn.LayerNorm(d_model)
@@ -273,6 +280,7 @@ class TransformerEncoderLayer(nn.Module):
         meta = self._meta
         meta.eps = float(self.pre_norm.eps)
         meta.robust = self.self_attn.robust
+        meta.attn_dropout_fused = self.self_attn.fused_attention_dropout
         pa = float(self.self_attn.attn_drop.p) if self.training else 0.0
         if not 0.0 <= pa < 1.0:
             raise NotImplementedError(f"attention dropout probability {pa} outside [0, 1)")
@@ -458,7 +466,7 @@ class TransformerClassifier(nn.Module):
                  stochastic_depth_rate=0.1,
                  positional_embedding='sine',
                  sequence_length=None,
-                 *args, robust=False, **kwargs):
+                 *args, robust=False, fused_attention_dropout=False, **kwargs):
         super().__init__()
         assert positional_embedding in {'sine', 'learnable', 'none'}
 
@@ -498,7 +506,8 @@ class TransformerClassifier(nn.Module):
         self.blocks = nn.ModuleList([
             TransformerEncoderLayer(d_model=embedding_dim, nhead=num_heads,
                                     dim_feedforward=dim_feedforward, dropout=dropout_rate,
-                                    attention_dropout=attention_dropout, drop_path_rate=layer_dpr, robust=robust)
+                                    attention_dropout=attention_dropout, drop_path_rate=layer_dpr, robust=robust,
+                                    fused_attention_dropout=fused_attention_dropout)
             for layer_dpr in dpr])
         for i, blk in enumerate(self.blocks):
             blk._site = -(2 + i)
@@ -566,7 +575,7 @@ class CCT(nn.Module):
         pooling_kernel_size=3,
         pooling_stride=2,
         pooling_padding=1,
-        *args, robust=False, attention_dropout=0.1, **kwargs
+        *args, robust=False, attention_dropout=0.1, fused_attention_dropout=False, **kwargs
     ):
         super().__init__()
         img_height, img_width = pair(img_size)
@@ -595,6 +604,7 @@ class CCT(nn.Module):
             attention_dropout=attention_dropout,
             stochastic_depth=0.1,
             robust=robust,
+            fused_attention_dropout=fused_attention_dropout,
             *args, **kwargs)
 
     def grad_groups(self):

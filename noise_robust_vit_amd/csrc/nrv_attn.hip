@@ -29,6 +29,10 @@ NRV_INTERNAL int nrv_attn_gen_supported(int B, int N, int H, int dh);
 NRV_INTERNAL int nrv_attn_gen_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, int dh, float scale, hipStream_t s);
 NRV_INTERNAL int nrv_attn_gen_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws,
                      int B, int N, int H, int dh, float scale, hipStream_t s);
+NRV_INTERNAL int nrv_attn_gen_drop_fwd(const void* qkv, void* out, float* lse, const unsigned long long* seed, unsigned T, float rs,
+                     int B, int N, int H, int dh, float scale, hipStream_t s);
+NRV_INTERNAL int nrv_attn_gen_drop_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws,
+                     const unsigned long long* seed, unsigned T, float rs, int B, int N, int H, int dh, float scale, hipStream_t s);
 NRV_INTERNAL int nrv_attn_gen_probs(const void* qkv, const float* lse, float* probs, int B, int N, int H, int dh, float scale, hipStream_t s);
 
 namespace {
@@ -48,6 +52,10 @@ struct AttnParams {
     // NRV_LAYOUT_BLOCKED : qkv [3*H][B*N][64]  (q_rs = 64, q_ws = H B N 64, q_hs = B N 64, q_bs = N 64), o [H][B*N][64]:
     //                      every head slice [N x 64] is ONE contiguous 128 N bytes instead of N segments of 128 bytes
     long long q_rs, q_ws, q_hs, q_bs, o_rs, o_hs, o_bs;
+    // DROP instantiations (nrv_attn_drop_*): 64-bit seed in device memory, threshold T of the 16-bit decisions, 1 / (1 - T / 2^16)
+    const unsigned long long* seed;
+    unsigned drop_T;
+    float drop_rs;
 };
 
 void set_layout(AttnParams& p, int layout, int dh) {
@@ -79,7 +87,9 @@ constexpr int atf_waves() { return NT <= 2 ? 1 : NT <= 4 ? 2 : 4; }
 
 // NT = number of 16-key tiles = image rows / 16.  N = 196 / 197 => NT = 13: 2 x 13 x 2 KiB = 53,248 B of LDS, THREE
 // workgroups per CU (with rows padded to 32 it would be 57,344 B and two).
-template <int NT>
+// DROP: attention-weight dropout.  The row statistics are those of the undropped row; the dropped weights become zero in the
+// bf16 P^T operand (decisions per key tile inside the exp loop: two words live) and 1 / (1 - p_eff) joins the final 1 / l.
+template <int NT, bool DROP>
 __global__ __launch_bounds__(64 * atf_waves<NT>(), NT <= 13 ? 3 : 2) void attn_fwd_fat_kernel(const AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NP = NT * 16;                // image rows
@@ -88,7 +98,8 @@ __global__ __launch_bounds__(64 * atf_waves<NT>(), NT <= 13 ? 3 : 2) void attn_f
     constexpr int NJ = 2 * NP / 8;             // DMA instructions (1 KiB = 8 rows each): K rows then V rows
     constexpr int ATF_WAVES = atf_waves<NT>();
     constexpr int JPW = NJ / ATF_WAVES;        // = NT with four waves
-    constexpr int MT = (NT == 13 || NT == 14) ? 1 : 2;   // trailing key tiles that can hold padding rows (launch_fwd_fat rounds other counts up to even)
+    // trailing key tiles that can hold padding rows (launch_fwd_fat rounds other counts up to even; with DROP it sends 13 tiles to 14)
+    constexpr int MT = (NT == 13 || (NT == 14 && !DROP)) ? 1 : 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int N = p.N, H = p.H;
     const long long ldq = p.q_rs;
@@ -189,6 +200,13 @@ __global__ __launch_bounds__(64 * atf_waves<NT>(), NT <= 13 ? 3 : 2) void attn_f
             mm = fmaxf(mm, __shfl_xor(mm, 32, 64));
             mm *= sc;                                               // sc > 0: max commutes with the scaling
             float ll = 0.f;
+            unsigned ag = 0u, a1 = 0u;
+            if constexpr (DROP) {
+                const unsigned long long seed = *p.seed;
+                const unsigned q = (unsigned)(q0 + t * 16);
+                ag = drop_row_key(drop_head_key(seed, blockIdx.x, DROP_C0), q) + 2u * g * DROP_GOLD;
+                a1 = drop_row_key(drop_head_key(seed, blockIdx.x, DROP_C1), q);
+            }
 #pragma unroll
             for (int kt = 0; kt < NT; ++kt) {
 #pragma unroll
@@ -198,6 +216,7 @@ __global__ __launch_bounds__(64 * atf_waves<NT>(), NT <= 13 ? 3 : 2) void attn_f
                     st[t][kt][e] = pv;
                     ll += pv;
                 }
+                if constexpr (DROP) drop_quad(st[t][kt], ag, a1, kt * 8, p.drop_T, 1.0f);
                 if (kt & 1) pf[t][kt >> 1] = pack_frag(st[t][kt - 1], st[t][kt]);
                 else if (kt == NT - 1) pf[t][kt >> 1] = pack_frag(st[t][kt], f32x4_t{0.f, 0.f, 0.f, 0.f});
             }
@@ -231,7 +250,7 @@ __global__ __launch_bounds__(64 * atf_waves<NT>(), NT <= 13 ? 3 : 2) void attn_f
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int q = q0 + t * 16;
-            const float inv = 1.0f / l[t];
+            const float inv = DROP ? p.drop_rs / l[t] : 1.0f / l[t];
             u32x4_t ov[2];
 #pragma unroll
             for (int pr = 0; pr < 2; ++pr) {
@@ -299,7 +318,7 @@ __device__ __forceinline__ void dma_two_images(char* smem, const bf16_t* src0, l
     }
 }
 
-template <int NT>
+template <int NT, bool DROP>
 __global__ __launch_bounds__(64 * atf_waves<NT>(), NT <= 13 ? 3 : 2) void attn_bwd_dq_fat_kernel(const AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int ATF_WAVES = atf_waves<NT>();
@@ -352,6 +371,16 @@ __global__ __launch_bounds__(64 * atf_waves<NT>(), NT <= 13 ? 3 : 2) void attn_b
     const bf16x4_t zero4 = {0, 0, 0, 0};
     for (int pair = wave; pair < npairs; pair += ATF_WAVES) {
         f32x4_t dq[2][4];
+        unsigned ag[2] = {0u, 0u}, a1[2] = {0u, 0u};        // DROP: the row keys of this lane's two queries
+        if constexpr (DROP) {
+            const unsigned long long seed = *p.seed;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const unsigned q = (unsigned)(pair * 32 + t * 16 + qc);
+                ag[t] = drop_row_key(drop_head_key(seed, blockIdx.x, DROP_C0), q) + 2u * g * DROP_GOLD;
+                a1[t] = drop_row_key(drop_head_key(seed, blockIdx.x, DROP_C1), q);
+            }
+        }
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -359,6 +388,26 @@ __global__ __launch_bounds__(64 * atf_waves<NT>(), NT <= 13 ? 3 : 2) void attn_b
         auto step = [&](const int kk, auto last_c) {
             constexpr bool LAST = decltype(last_c)::value;      // the last step: padding rows, and no upper half when NT is odd
             f32x4_t ds[2][2];                                   // [tile][half]
+            // DROP: the step's 16 decisions first (lane masks: they sit in scalar registers), so that the words' temporaries are
+            // dead before the fragments and accumulators below are live
+            bool kept[2][2][4] = {};
+            if constexpr (DROP) {
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf) {
+                    if (!LAST || hf == 0 || (NT % 2 == 0)) {
+#pragma unroll
+                        for (int t = 0; t < 2; ++t) {
+#pragma unroll
+                            for (int j = 0; j < 2; ++j) {
+                                const unsigned w = drop_word(ag[t], a1[t], (unsigned)((2 * kk + hf) * 8 + j));
+                                kept[hf][t][2 * j] = (w & 0xffffu) >= p.drop_T;
+                                kept[hf][t][2 * j + 1] = (w >> 16) >= p.drop_T;
+                            }
+                        }
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
                 const int kt = 2 * kk + hf;
@@ -381,7 +430,8 @@ __global__ __launch_bounds__(64 * atf_waves<NT>(), NT <= 13 ? 3 : 2) void attn_b
                         for (int e = 0; e < 4; ++e) {
                             float pv = __builtin_amdgcn_exp2f(fmaf(st[e], sc, -lse2[t]));
                             if (LAST) pv = (kt * 16 + 4 * g + e < N) ? pv : 0.f;
-                            ds[t][hf][e] = pv * (dp[e] - dl[t]);
+                            if constexpr (DROP) ds[t][hf][e] = pv * ((kept[hf][t][e] ? dp[e] * p.drop_rs : 0.f) - dl[t]);   // M o dP, before - delta
+                            else ds[t][hf][e] = pv * (dp[e] - dl[t]);
                         }
                     }
                 } else {
@@ -425,7 +475,9 @@ __global__ __launch_bounds__(64 * atf_waves<NT>(), NT <= 13 ? 3 : 2) void attn_b
     }
 }
 
-template <int NT>
+// DROP: the two row keys of every query sit in LDS behind lse / delta; a lane (one key, four consecutive queries) draws one
+// word per element and uses its key's half.  P o keep feeds dV (1 / (1 - p_eff) at the store), M o dP feeds dS.
+template <int NT, bool DROP>
 __global__ __launch_bounds__(64 * atf_waves<NT>(), 2) void attn_bwd_dkv_fat_kernel(const AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int ATF_WAVES = atf_waves<NT>(), ATF_THREADS = 64 * ATF_WAVES;
@@ -436,6 +488,8 @@ __global__ __launch_bounds__(64 * atf_waves<NT>(), 2) void attn_bwd_dkv_fat_kern
     const char* doimg = smem + NP * 128;
     float* lse2s = reinterpret_cast<float*>(smem + 2 * NP * 128);
     float* dels = lse2s + NPS;
+    unsigned* a0s = reinterpret_cast<unsigned*>(dels + NPS);      // DROP
+    unsigned* a1s = a0s + NPS;                                   // DROP
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int N = p.N, H = p.H;
     const int b = blockIdx.x / H, h = blockIdx.x - b * H;
@@ -464,6 +518,11 @@ __global__ __launch_bounds__(64 * atf_waves<NT>(), 2) void attn_bwd_dkv_fat_kern
         const long long sidx = ((long long)b * H + h) * N + i;
         lse2s[i] = i < N ? p.lse[sidx] * LOG2E : INFINITY;     // exp2(s - inf) = 0 for padded queries
         dels[i] = i < N ? p.delta[sidx] : 0.f;
+        if constexpr (DROP) {
+            const unsigned long long seed = *p.seed;
+            a0s[i] = drop_row_key(drop_head_key(seed, blockIdx.x, DROP_C0), (unsigned)i);
+            a1s[i] = drop_row_key(drop_head_key(seed, blockIdx.x, DROP_C1), (unsigned)i);
+        }
     }
     dma_two_images<NT>(smem, qbase, ldq, dobase, ldo, N, wave, lane);
     __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -491,6 +550,25 @@ __global__ __launch_bounds__(64 * atf_waves<NT>(), 2) void attn_bwd_dkv_fat_kern
         auto step = [&](const int qq, auto last_c) {
             constexpr bool LAST = decltype(last_c)::value;      // the last step has no upper half when NT is odd
             f32x4_t pt[2][2], ds[2][2];                         // [key tile][query half]
+            // DROP: the step's 16 decisions first (lane masks in scalar registers), as in the dq kernel
+            bool kept[2][2][4] = {};
+            if constexpr (DROP) {
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf) {
+                    if (!LAST || hf == 0 || (NT % 2 == 0)) {
+                        const u32x4_t r0 = *reinterpret_cast<const u32x4_t*>(a0s + (2 * qq + hf) * 16 + 4 * g);
+                        const u32x4_t r1 = *reinterpret_cast<const u32x4_t*>(a1s + (2 * qq + hf) * 16 + 4 * g);
+#pragma unroll
+                        for (int t = 0; t < 2; ++t) {
+                            const unsigned key = (unsigned)(pair * 32 + t * 16 + kc);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                kept[hf][t][e] = drop_keep(drop_word(r0[e], r1[e], key >> 1), key, p.drop_T);
+                        }
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
                 const int qt = 2 * qq + hf;
@@ -514,8 +592,13 @@ __global__ __launch_bounds__(64 * atf_waves<NT>(), 2) void attn_bwd_dkv_fat_kern
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const float pv = __builtin_amdgcn_exp2f(fmaf(st[e], sc, -l4[e]));
-                            pt[t][hf][e] = pv;
-                            ds[t][hf][e] = pv * (dp[e] - d4[e]);
+                            if constexpr (DROP) {
+                                pt[t][hf][e] = kept[hf][t][e] ? pv : 0.f;
+                                ds[t][hf][e] = pv * ((kept[hf][t][e] ? dp[e] * p.drop_rs : 0.f) - d4[e]);
+                            } else {
+                                pt[t][hf][e] = pv;
+                                ds[t][hf][e] = pv * (dp[e] - d4[e]);
+                            }
                         }
                     }
                 } else {
@@ -553,64 +636,67 @@ __global__ __launch_bounds__(64 * atf_waves<NT>(), 2) void attn_bwd_dkv_fat_kern
             const int key = k0 + t * 16;
             bf16_t* row = p.dqkv + (long long)b * p.q_bs + h * p.q_hs + (long long)(key < N ? key : 0) * ldq;
             store_tile_bf16(row + p.q_ws, dk[t], p.scale, g, key < N);
-            store_tile_bf16(row + 2 * p.q_ws, dv[t], 1.0f, g, key < N);
+            store_tile_bf16(row + 2 * p.q_ws, dv[t], DROP ? p.drop_rs : 1.0f, g, key < N);
         }
     }
 }
 
-template <int NT>
+template <int NT, bool DROP>
 int launch_fwd_fat_nt(const AttnParams& p, hipStream_t s) {
     constexpr int lds = 2 * NT * 16 * 128;
-    static int attr = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_fat_kernel<NT>),
+    static int attr = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_fat_kernel<NT, DROP>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (attr != 0) return attr;
-    hipLaunchKernelGGL((attn_fwd_fat_kernel<NT>), dim3(p.B * p.H), dim3(64 * atf_waves<NT>()), lds, s, p);
+    hipLaunchKernelGGL((attn_fwd_fat_kernel<NT, DROP>), dim3(p.B * p.H), dim3(64 * atf_waves<NT>()), lds, s, p);
     NRV_CHECK_LAUNCH();
     return 0;
 }
 
 // key tiles: the instantiated counts cover every N <= 256 with at most one tile of padding, and 13 exactly (N = 196 / 197)
+template <bool DROP>
 int launch_fwd_fat(const AttnParams& p, hipStream_t s) {
     const int nt = (p.N + 15) / 16;
-    if (nt <= 2) return launch_fwd_fat_nt<2>(p, s);
-    if (nt <= 4) return launch_fwd_fat_nt<4>(p, s);
-    if (nt <= 6) return launch_fwd_fat_nt<6>(p, s);
-    if (nt <= 8) return launch_fwd_fat_nt<8>(p, s);
-    if (nt <= 10) return launch_fwd_fat_nt<10>(p, s);
-    if (nt <= 12) return launch_fwd_fat_nt<12>(p, s);
-    if (nt == 13) return launch_fwd_fat_nt<13>(p, s);
-    if (nt == 14) return launch_fwd_fat_nt<14>(p, s);
-    return launch_fwd_fat_nt<16>(p, s);
+    if (nt <= 2) return launch_fwd_fat_nt<2, DROP>(p, s);
+    if (nt <= 4) return launch_fwd_fat_nt<4, DROP>(p, s);
+    if (nt <= 6) return launch_fwd_fat_nt<6, DROP>(p, s);
+    if (nt <= 8) return launch_fwd_fat_nt<8, DROP>(p, s);
+    if (nt <= 10) return launch_fwd_fat_nt<10, DROP>(p, s);
+    if (nt <= 12) return launch_fwd_fat_nt<12, DROP>(p, s);
+    // the 13-tile form has no register left under its three-workgroup cap: with dropout N = 196 / 197 run the 14-tile form
+    if (nt == 13) return launch_fwd_fat_nt<DROP ? 14 : 13, DROP>(p, s);
+    if (nt == 14) return launch_fwd_fat_nt<14, DROP>(p, s);
+    return launch_fwd_fat_nt<16, DROP>(p, s);
 }
 
-template <int NT>
+template <int NT, bool DROP>
 int launch_bwd_fat_nt(const AttnParams& p, hipStream_t s) {
     constexpr int lds_dq = 2 * NT * 16 * 128;
-    constexpr int lds_dkv = 2 * NT * 16 * 128 + 2 * ((NT + 1) / 2) * 32 * 4;
-    static int a1 = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_fat_kernel<NT>),
+    constexpr int lds_dkv = 2 * NT * 16 * 128 + (DROP ? 4 : 2) * ((NT + 1) / 2) * 32 * 4;      // lse, delta (+ two row keys) per query
+    static int a1 = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_fat_kernel<NT, DROP>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_dq);
-    static int a2 = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_fat_kernel<NT>),
+    static int a2 = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_fat_kernel<NT, DROP>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_dkv);
     if (a1 != 0) return a1;
     if (a2 != 0) return a2;
-    hipLaunchKernelGGL((attn_bwd_dq_fat_kernel<NT>), dim3(p.B * p.H), dim3(64 * atf_waves<NT>()), lds_dq, s, p);
+    hipLaunchKernelGGL((attn_bwd_dq_fat_kernel<NT, DROP>), dim3(p.B * p.H), dim3(64 * atf_waves<NT>()), lds_dq, s, p);
     NRV_CHECK_LAUNCH();
-    hipLaunchKernelGGL((attn_bwd_dkv_fat_kernel<NT>), dim3(p.B * p.H), dim3(64 * atf_waves<NT>()), lds_dkv, s, p);
+    hipLaunchKernelGGL((attn_bwd_dkv_fat_kernel<NT, DROP>), dim3(p.B * p.H), dim3(64 * atf_waves<NT>()), lds_dkv, s, p);
     NRV_CHECK_LAUNCH();
     return 0;
 }
 
+template <bool DROP>
 int launch_bwd_fat(const AttnParams& p, hipStream_t s) {
     const int nt = (p.N + 15) / 16;
-    if (nt <= 2) return launch_bwd_fat_nt<2>(p, s);
-    if (nt <= 4) return launch_bwd_fat_nt<4>(p, s);
-    if (nt <= 6) return launch_bwd_fat_nt<6>(p, s);
-    if (nt <= 8) return launch_bwd_fat_nt<8>(p, s);
-    if (nt <= 10) return launch_bwd_fat_nt<10>(p, s);
-    if (nt <= 12) return launch_bwd_fat_nt<12>(p, s);
-    if (nt == 13) return launch_bwd_fat_nt<13>(p, s);
-    if (nt == 14) return launch_bwd_fat_nt<14>(p, s);
-    return launch_bwd_fat_nt<16>(p, s);
+    if (nt <= 2) return launch_bwd_fat_nt<2, DROP>(p, s);
+    if (nt <= 4) return launch_bwd_fat_nt<4, DROP>(p, s);
+    if (nt <= 6) return launch_bwd_fat_nt<6, DROP>(p, s);
+    if (nt <= 8) return launch_bwd_fat_nt<8, DROP>(p, s);
+    if (nt <= 10) return launch_bwd_fat_nt<10, DROP>(p, s);
+    if (nt <= 12) return launch_bwd_fat_nt<12, DROP>(p, s);
+    if (nt == 13) return launch_bwd_fat_nt<13, DROP>(p, s);
+    if (nt == 14) return launch_bwd_fat_nt<14, DROP>(p, s);
+    return launch_bwd_fat_nt<16, DROP>(p, s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -649,6 +735,27 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const AttnParams p, flo
     }
 }
 
+// the keep decisions themselves, uint8 [B, H, N, N]: what the DROP kernels regenerate on chip (tests, and the composed path
+// as their reference).  One thread per element, the grid covers them all.
+__global__ __launch_bounds__(256) void attn_drop_mask_kernel(const unsigned long long* __restrict__ seed_dev, unsigned T,
+                                                             unsigned char* __restrict__ keep, long long total, int N) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long long row = i / N;                       // g * N + q
+    const unsigned key = (unsigned)(i - row * N);
+    const unsigned g = (unsigned)(row / N), q = (unsigned)(row - (long long)g * N);
+    const unsigned long long seed = *seed_dev;
+    const unsigned a0 = drop_row_key(drop_head_key(seed, g, DROP_C0), q), a1 = drop_row_key(drop_head_key(seed, g, DROP_C1), q);
+    keep[i] = drop_keep(drop_word(a0, a1, key >> 1), key, T) ? 1 : 0;
+}
+
+// T = round(p * 2^16) of a dropout probability, or NRV_ERR_SHAPE (p < 0, NaN, or a T of 65536: p_eff would be 1)
+int drop_threshold(float p) {
+    if (!(p >= 0.f) || !(p < 1.f)) return NRV_ERR_SHAPE;
+    const int T = (int)((double)p * 65536.0 + 0.5);
+    return T > 65535 ? NRV_ERR_SHAPE : T;
+}
+
 // shape class of a call: 1 = the single-pass kernels of this file (dh 64, N <= 256), 2 = the streaming kernels of
 // nrv_attn_gen.hip (any N, dh 32 / 64 / 80 / 96 / 128), 0 = not supported
 int shape_class(int B, int N, int H, int dh) {
@@ -681,7 +788,7 @@ extern "C" int nrv_attn_fwd(const void* qkv_bf16, void* out_bf16, float* lse,
     p.B = B; p.N = N; p.H = H; p.scale = scale;
     set_layout(p, layout, dh);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return launch_fwd_fat(p, s);
+    return launch_fwd_fat<false>(p, s);
 }
 
 extern "C" int nrv_attn_bwd(const void* qkv_bf16, const void* out_bf16, const void* dout_bf16, const float* lse,
@@ -704,7 +811,7 @@ extern "C" int nrv_attn_bwd(const void* qkv_bf16, const void* out_bf16, const vo
     p.B = B; p.N = N; p.H = H; p.scale = scale;
     set_layout(p, layout, dh);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return launch_bwd_fat(p, s);
+    return launch_bwd_fat<false>(p, s);
 }
 
 extern "C" int nrv_attn_probs(const void* qkv_bf16, const float* lse, float* probs,
@@ -721,6 +828,73 @@ extern "C" int nrv_attn_probs(const void* qkv_bf16, const float* lse, float* pro
     p.B = B; p.N = N; p.H = H; p.scale = scale;
     set_layout(p, layout, dh);
     hipLaunchKernelGGL(attn_probs_kernel, dim3((unsigned)(B * H), (unsigned)((N + 15) / 16)), dim3(256), 0, s, p, probs);
+    NRV_CHECK_LAUNCH();
+    return 0;
+}
+
+// Attention-weight dropout inside the kernels above (row-major layout only).  T = 0 runs the plain instantiations.
+extern "C" int nrv_attn_drop_threshold(float p) { return drop_threshold(p); }
+
+extern "C" int nrv_attn_drop_fwd(const void* qkv_bf16, void* out_bf16, float* lse, const uint64_t* seed_dev, float p,
+                                 int B, int N, int H, int dh, float scale, void* stream) {
+    if (!qkv_bf16 || !out_bf16 || !lse || !seed_dev) return NRV_ERR_NULL;
+    const int cls = shape_class(B, N, H, dh);
+    const int T = drop_threshold(p);
+    if (cls == 0 || T < 0 || !layout_ok(0, cls, B, N, H, dh)) return NRV_ERR_SHAPE;
+    if (!nrv_aligned16(qkv_bf16) || !nrv_aligned16(out_bf16) || (reinterpret_cast<uintptr_t>(seed_dev) & 7u)) return NRV_ERR_ALIGN;
+    if (T == 0) return nrv_attn_fwd(qkv_bf16, out_bf16, lse, B, N, H, dh, scale, 0, stream);
+    const float rs = (float)(65536.0 / (65536.0 - T));
+    const unsigned long long* seed = reinterpret_cast<const unsigned long long*>(seed_dev);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (cls == 2) return nrv_attn_gen_drop_fwd(qkv_bf16, out_bf16, lse, seed, (unsigned)T, rs, B, N, H, dh, scale, s);
+    AttnParams q{};
+    q.qkv = static_cast<const bf16_t*>(qkv_bf16);
+    q.o = static_cast<bf16_t*>(out_bf16);
+    q.lse = lse;
+    q.B = B; q.N = N; q.H = H; q.scale = scale;
+    q.seed = seed; q.drop_T = (unsigned)T; q.drop_rs = rs;
+    set_layout(q, 0, dh);
+    return launch_fwd_fat<true>(q, s);
+}
+
+extern "C" int nrv_attn_drop_bwd(const void* qkv_bf16, const void* out_bf16, const void* dout_bf16, const float* lse,
+                                 void* dqkv_bf16, float* delta_ws, const uint64_t* seed_dev, float p,
+                                 int B, int N, int H, int dh, float scale, void* stream) {
+    if (!qkv_bf16 || !out_bf16 || !dout_bf16 || !lse || !dqkv_bf16 || !delta_ws || !seed_dev) return NRV_ERR_NULL;
+    const int cls = shape_class(B, N, H, dh);
+    const int T = drop_threshold(p);
+    if (cls == 0 || T < 0 || !layout_ok(0, cls, B, N, H, dh)) return NRV_ERR_SHAPE;
+    if (!nrv_aligned16(qkv_bf16) || !nrv_aligned16(out_bf16) || !nrv_aligned16(dout_bf16) || !nrv_aligned16(dqkv_bf16) ||
+        (reinterpret_cast<uintptr_t>(seed_dev) & 7u))
+        return NRV_ERR_ALIGN;
+    if (T == 0) return nrv_attn_bwd(qkv_bf16, out_bf16, dout_bf16, lse, dqkv_bf16, delta_ws, B, N, H, dh, scale, 0, stream);
+    const float rs = (float)(65536.0 / (65536.0 - T));
+    const unsigned long long* seed = reinterpret_cast<const unsigned long long*>(seed_dev);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (cls == 2)
+        return nrv_attn_gen_drop_bwd(qkv_bf16, out_bf16, dout_bf16, lse, dqkv_bf16, delta_ws, seed, (unsigned)T, rs, B, N, H, dh, scale, s);
+    AttnParams q{};
+    q.qkv = static_cast<const bf16_t*>(qkv_bf16);
+    q.out = static_cast<const bf16_t*>(out_bf16);
+    q.dout = static_cast<const bf16_t*>(dout_bf16);
+    q.dqkv = static_cast<bf16_t*>(dqkv_bf16);
+    q.lse = const_cast<float*>(lse);
+    q.delta = delta_ws;
+    q.B = B; q.N = N; q.H = H; q.scale = scale;
+    q.seed = seed; q.drop_T = (unsigned)T; q.drop_rs = rs;
+    set_layout(q, 0, dh);
+    return launch_bwd_fat<true>(q, s);
+}
+
+extern "C" int nrv_attn_drop_mask(const uint64_t* seed_dev, float p, unsigned char* keep, int B, int H, int N, void* stream) {
+    if (!seed_dev || !keep) return NRV_ERR_NULL;
+    const int T = drop_threshold(p);
+    if (B <= 0 || H <= 0 || N <= 0 || T < 0 || (long long)B * H > 0x7fffffffll) return NRV_ERR_SHAPE;
+    if ((long long)N * N > 0x7fffffffll * 256 / ((long long)B * H)) return NRV_ERR_SHAPE;     // blocks of 256 elements fit a grid
+    if (reinterpret_cast<uintptr_t>(seed_dev) & 7u) return NRV_ERR_ALIGN;
+    const long long total = (long long)B * H * N * N;
+    hipLaunchKernelGGL(attn_drop_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const unsigned long long*>(seed_dev), (unsigned)T, keep, total, N);
     NRV_CHECK_LAUNCH();
     return 0;
 }

@@ -62,5 +62,49 @@ __device__ __forceinline__ bf16x8_t row_frag_img(const char* img, int rb, int ks
     return lds_read_b128(img + img_off(rb + (lane & 15), ks * 4 + (lane >> 4)));
 }
 
+// ---------------------------------------------------------------------------------------------
+// attention-weight dropout: the keep decisions of include/nrv.h ("Attention-weight dropout"), a stateless function of
+// (seed, g = b * H + h, query, key).  A query has two 32-bit ROW KEYS (four chained avalanches over seed, g and q: computed
+// once per row, in registers by the query-owner kernels, in LDS by the key-owner ones); a (query, key PAIR) has one 32-bit
+// WORD (two multiplies), whose low half decides the even key of the pair and whose high half the odd one.
+// ---------------------------------------------------------------------------------------------
+constexpr unsigned DROP_GOLD = 0x9E3779B9u, DROP_M1 = 0x85EBCA6Bu, DROP_M2 = 0xC2B2AE35u;
+constexpr unsigned DROP_C0 = 0x9E3779B9u, DROP_C1 = 0x7F4A7C15u;       // the chains of row keys a0 and a1 start from these
+
+__host__ __device__ __forceinline__ unsigned drop_fmix(unsigned h) {
+    h ^= h >> 16;
+    h *= DROP_M1;
+    h ^= h >> 13;
+    h *= DROP_M2;
+    return h ^ (h >> 16);
+}
+// the part of a row key that a (sample, head) shares
+__host__ __device__ __forceinline__ unsigned drop_head_key(unsigned long long seed, unsigned g, unsigned c) {
+    return drop_fmix(drop_fmix(drop_fmix((unsigned)seed + c) ^ (unsigned)(seed >> 32)) + g);
+}
+__host__ __device__ __forceinline__ unsigned drop_row_key(unsigned head_key, unsigned q) { return drop_fmix(head_key ^ q); }
+// word of (row keys a0, a1; key pair kp = key >> 1)
+__host__ __device__ __forceinline__ unsigned drop_word(unsigned a0, unsigned a1, unsigned kp) {
+    unsigned t = a0 + kp * DROP_GOLD;
+    t ^= t >> 16;
+    t *= DROP_M1;
+    t ^= a1;
+    t ^= t >> 13;
+    t *= DROP_M2;
+    return t ^ (t >> 16);
+}
+__host__ __device__ __forceinline__ bool drop_keep(unsigned word, unsigned key, unsigned T) {
+    return ((word >> ((key & 1u) << 4)) & 0xffffu) >= T;
+}
+// a lane's four consecutive keys 4 j .. 4 j + 3 of one query (the score accumulator's e = 0..3): two words.  `ag` = a0 + the
+// lane's share of the pair index times DROP_GOLD, `kp` = the rest of the pair index (a constant where the loop is unrolled)
+__device__ __forceinline__ void drop_quad(f32x4_t& v, unsigned ag, unsigned a1, unsigned kp, unsigned T, float keep_mul) {
+    const unsigned w0 = drop_word(ag, a1, kp), w1 = drop_word(ag, a1, kp + 1);
+    v[0] = (w0 & 0xffffu) >= T ? v[0] * keep_mul : 0.f;
+    v[1] = (w0 >> 16) >= T ? v[1] * keep_mul : 0.f;
+    v[2] = (w1 & 0xffffu) >= T ? v[2] * keep_mul : 0.f;
+    v[3] = (w1 >> 16) >= T ? v[3] * keep_mul : 0.f;
+}
+
 
 }  // namespace nrv_attn

@@ -44,6 +44,14 @@ namespace {
 using nrv_attn::LN2;
 using nrv_attn::LOG2E;
 using nrv_attn::pack_frag;
+using nrv_attn::DROP_C0;
+using nrv_attn::DROP_C1;
+using nrv_attn::DROP_GOLD;
+using nrv_attn::drop_head_key;
+using nrv_attn::drop_keep;
+using nrv_attn::drop_quad;
+using nrv_attn::drop_row_key;
+using nrv_attn::drop_word;
 
 struct GenParams {
     const bf16_t* qkv;       // [B*Nq, 3*H*dh]
@@ -61,6 +69,10 @@ struct GenParams {
     float* dmem;             // MEM: bwd output, memory rows [B*M, 2*H*dh]
     long long mstride;       // MEM: memory rows per sample step, 0 or M
     long long mask_bs, mask_hs;
+    // DROP instantiations (nrv_attn_drop_*): 64-bit seed in device memory, threshold T of the 16-bit decisions, 1 / (1 - T / 2^16)
+    const unsigned long long* seed;
+    unsigned drop_T;
+    float drop_rs;
 };
 
 constexpr int GT = 64;          // rows of a streamed tile = rows owned by a workgroup (4 waves x 16)
@@ -189,8 +201,11 @@ __device__ __forceinline__ void mask_words(const GenParams& p, int b, int h, int
 // ---------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------
-template <int KS, bool MEM>
+// DROP (MEM = false only): attention-weight dropout.  m and l are those of the undropped row; the dropped weights become zero in
+// the bf16 P^T operand and 1 / (1 - p_eff) joins the final 1 / l.
+template <int KS, bool MEM, bool DROP>
 __global__ __launch_bounds__(GEN_THREADS) void attn_gen_fwd_kernel(const GenParams p) {
+    static_assert(!(MEM && DROP), "no dropout with memory keys / score masks");
     using C = GenCfg<KS>;
     __shared__ __attribute__((aligned(16))) char smem[2 * C::TILE];
     char* kimg = smem;
@@ -215,6 +230,12 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_gen_fwd_kernel(const GenPara
 #pragma unroll
     for (int dt = 0; dt < C::DT; ++dt) ot[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
+    unsigned ag = 0u, a1 = 0u;                            // DROP: the row keys of this lane's query
+    if constexpr (DROP) {
+        const unsigned long long seed = *p.seed;
+        ag = drop_row_key(drop_head_key(seed, (unsigned)bh, DROP_C0), (unsigned)q) + 2u * g * DROP_GOLD;
+        a1 = drop_row_key(drop_head_key(seed, (unsigned)bh, DROP_C1), (unsigned)q);
+    }
     u32x4_t kreg[KS], vreg[KS];                           // the next K / V tile, requested one tile ahead
     fetch_kv<KS, MEM>(kreg, vreg, p, kbase, b, h, 0, tid);
     for (int k0 = 0; k0 < Nk; k0 += GT) {
@@ -258,6 +279,10 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_gen_fwd_kernel(const GenPara
             }
         l = l * alpha + quad_sum(ps);
         m = mn;
+        if constexpr (DROP) {
+#pragma unroll
+            for (int sub = 0; sub < 4; ++sub) drop_quad(st[sub], ag, a1, (unsigned)(k0 >> 1) + sub * 8, p.drop_T, 1.0f);
+        }
 #pragma unroll
         for (int dt = 0; dt < C::DT; ++dt) ot[dt] *= alpha;
         // O^T += V^T P^T, two 32-key steps
@@ -269,7 +294,7 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_gen_fwd_kernel(const GenPara
         }
     }
     if (q < N) {
-        const float inv = 1.0f / l;
+        const float inv = DROP ? p.drop_rs / l : 1.0f / l;
         bf16_t* dst = p.o + ((long long)b * N + q) * ((long long)H * dh) + h * dh;
 #pragma unroll
         for (int dt = 0; dt < C::DT; ++dt) {
@@ -283,8 +308,9 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_gen_fwd_kernel(const GenPara
 // ---------------------------------------------------------------------------------------------
 // backward, query-owner pass: dQ = scale * dS K with dS = P o (dP - delta), dP = dO V^T; also writes delta = rowsum(dO o O)
 // ---------------------------------------------------------------------------------------------
-template <int KS, bool MEM>
+template <int KS, bool MEM, bool DROP>
 __global__ __launch_bounds__(GEN_THREADS) void attn_gen_dq_kernel(const GenParams p) {
+    static_assert(!(MEM && DROP), "no dropout with memory keys / score masks");
     using C = GenCfg<KS>;
     __shared__ __attribute__((aligned(16))) char smem[2 * C::TILE];
     char* kimg = smem;
@@ -320,6 +346,12 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_gen_dq_kernel(const GenParam
     const float lse2 = q < N && !(MEM && lsev == MASKED) ? lsev * LOG2E : INFINITY;   // exp2(s - inf) = 0 for padded queries
     if (q < N && g == 0) p.delta[sidx] = dl;
 
+    unsigned ag = 0u, a1 = 0u;                            // DROP: the row keys of this lane's query
+    if constexpr (DROP) {
+        const unsigned long long seed = *p.seed;
+        ag = drop_row_key(drop_head_key(seed, (unsigned)bh, DROP_C0), (unsigned)q) + 2u * g * DROP_GOLD;
+        a1 = drop_row_key(drop_head_key(seed, (unsigned)bh, DROP_C1), (unsigned)q);
+    }
     f32x4_t dqt[C::DT];
 #pragma unroll
     for (int dt = 0; dt < C::DT; ++dt) dqt[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
@@ -342,6 +374,7 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_gen_dq_kernel(const GenParam
                 s = mfma16(row_frag<KS>(kimg, sub * 16, ks, lane), qf[ks], s);
                 dp = mfma16(row_frag<KS>(vimg, sub * 16, ks, lane), dof[ks], dp);
             }
+            if constexpr (DROP) drop_quad(dp, ag, a1, (unsigned)(k0 >> 1) + sub * 8, p.drop_T, p.drop_rs);     // M o dP, before - delta
             const unsigned w = sub < 2 ? mw0 : mw1;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -372,16 +405,20 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_gen_dq_kernel(const GenParam
 // backward, key-owner pass: dV = P^T dO, dK = scale * dS^T Q for 64 keys of one (batch, head).  Scores in [query][key]
 // orientation: a lane owns one key column, its queries sit in registers and are the k slots of the dV^T / dK^T products.
 // ---------------------------------------------------------------------------------------------
-template <int KS, bool MEM>
+template <int KS, bool MEM, bool DROP>
 __global__ __launch_bounds__(GEN_THREADS) void attn_gen_dkv_kernel(const GenParams p) {
+    static_assert(!(MEM && DROP), "no dropout with memory keys / score masks");
     using C = GenCfg<KS>;
-    // per-query words behind the two tiles: lse, delta; MEM adds the uniform P of a fully masked row and two mask words
-    __shared__ __attribute__((aligned(16))) char smem[2 * C::TILE + (MEM ? 5 : 2) * GT * 4];
+    // per-query words behind the two tiles: lse, delta; MEM adds the uniform P of a fully masked row and two mask words, DROP
+    // the two row keys of the dropout decisions
+    __shared__ __attribute__((aligned(16))) char smem[2 * C::TILE + (MEM ? 5 : DROP ? 4 : 2) * GT * 4];
     char* qimg = smem;
     char* doimg = smem + C::TILE;
     float* lse2s = reinterpret_cast<float*>(smem + 2 * C::TILE);
     float* dels = lse2s + GT;
     float* unis = dels + GT;                                         // MEM
+    unsigned* a0s = reinterpret_cast<unsigned*>(dels + GT);          // DROP
+    unsigned* a1s = a0s + GT;                                        // DROP
     unsigned* mws = reinterpret_cast<unsigned*>(unis + GT);          // MEM, [2][64]: the mask words of this block's keys per query
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, kc = lane & 15;
@@ -454,6 +491,11 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_gen_dkv_kernel(const GenPara
             lse2s[tid] = lreg;
             dels[tid] = dreg;
             if constexpr (MEM) unis[tid] = ureg;
+            if constexpr (DROP) {
+                const unsigned long long seed = *p.seed;
+                a0s[tid] = drop_row_key(drop_head_key(seed, (unsigned)bh, DROP_C0), (unsigned)(q0 + tid));
+                a1s[tid] = drop_row_key(drop_head_key(seed, (unsigned)bh, DROP_C1), (unsigned)(q0 + tid));
+            }
         } else if (MEM && tid < 3 * GT) {
             mws[tid - GT] = mreg;
         }
@@ -483,12 +525,23 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_gen_dkv_kernel(const GenPara
                 u4 = *reinterpret_cast<const f32x4_t*>(unis + sub * 16 + 4 * g);
                 w4 = *reinterpret_cast<const u32x4_t*>(mws + msel * GT + sub * 16 + 4 * g);
             }
+            u32x4_t r0 = {0u, 0u, 0u, 0u}, r1 = r0;
+            if constexpr (DROP) {
+                r0 = *reinterpret_cast<const u32x4_t*>(a0s + sub * 16 + 4 * g);
+                r1 = *reinterpret_cast<const u32x4_t*>(a1s + sub * 16 + 4 * g);
+            }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const bool keep = !MEM || ((w4[e] >> mbit) & 1u);   // masked pairs: P = 0 (1 / Nk in a fully masked row), dS = 0
                 const float pv = keep ? __builtin_amdgcn_exp2f(fmaf(s[e], sc, -l4[e])) : u4[e];
-                pt[sub][e] = pv;
-                ds[sub][e] = keep ? pv * (dp[e] - d4[e]) : 0.f;
+                if constexpr (DROP) {                               // P o keep feeds dV (1 / (1 - p_eff) at the store), M o dP feeds dS
+                    const bool kept = drop_keep(drop_word(r0[e], r1[e], (unsigned)key >> 1), (unsigned)key, p.drop_T);
+                    pt[sub][e] = kept ? pv : 0.f;
+                    ds[sub][e] = pv * ((kept ? dp[e] * p.drop_rs : 0.f) - d4[e]);
+                } else {
+                    pt[sub][e] = pv;
+                    ds[sub][e] = keep ? pv * (dp[e] - d4[e]) : 0.f;
+                }
             }
         }
 #pragma unroll
@@ -510,7 +563,7 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_gen_dkv_kernel(const GenPara
             const int d0 = dt * 16 + 4 * g;
             if (d0 < dh) {
                 nrv_attn::store_bf16x4(dk + d0, dkt[dt] * p.scale);
-                nrv_attn::store_bf16x4(dv + d0, dvt[dt]);
+                nrv_attn::store_bf16x4(dv + d0, DROP ? dvt[dt] * p.drop_rs : dvt[dt]);
             }
         }
     } else if constexpr (MEM) {
@@ -597,28 +650,28 @@ int ks_of(int dh) {
 }
 
 // forward: one workgroup per 64 queries; backward: the dQ pass over query blocks, then the dK / dV pass over key blocks
-template <int KS, bool MEM>
+template <int KS, bool MEM, bool DROP = false>
 int launch(const GenParams& p, bool bwd, hipStream_t s) {
     const long long gq = (long long)p.B * p.H * ((p.Nq + GT - 1) / GT);
     if (!bwd) {
-        hipLaunchKernelGGL((attn_gen_fwd_kernel<KS, MEM>), dim3((unsigned)gq), dim3(GEN_THREADS), 0, s, p);
+        hipLaunchKernelGGL((attn_gen_fwd_kernel<KS, MEM, DROP>), dim3((unsigned)gq), dim3(GEN_THREADS), 0, s, p);
         NRV_CHECK_LAUNCH();
         return 0;
     }
     const long long gk = (long long)p.B * p.H * ((p.Nk + GT - 1) / GT);
-    hipLaunchKernelGGL((attn_gen_dq_kernel<KS, MEM>), dim3((unsigned)gq), dim3(GEN_THREADS), 0, s, p);
+    hipLaunchKernelGGL((attn_gen_dq_kernel<KS, MEM, DROP>), dim3((unsigned)gq), dim3(GEN_THREADS), 0, s, p);
     NRV_CHECK_LAUNCH();
-    hipLaunchKernelGGL((attn_gen_dkv_kernel<KS, MEM>), dim3((unsigned)gk), dim3(GEN_THREADS), 0, s, p);
+    hipLaunchKernelGGL((attn_gen_dkv_kernel<KS, MEM, DROP>), dim3((unsigned)gk), dim3(GEN_THREADS), 0, s, p);
     NRV_CHECK_LAUNCH();
     return 0;
 }
-template <bool MEM>
-int launch(const GenParams& p, bool bwd, hipStream_t s) {
+template <bool MEM, bool DROP = false>
+int launch_dh(const GenParams& p, bool bwd, hipStream_t s) {
     switch (ks_of(p.dh)) {
-        case 1: return launch<1, MEM>(p, bwd, s);
-        case 2: return launch<2, MEM>(p, bwd, s);
-        case 3: return launch<3, MEM>(p, bwd, s);
-        case 4: return launch<4, MEM>(p, bwd, s);
+        case 1: return launch<1, MEM, DROP>(p, bwd, s);
+        case 2: return launch<2, MEM, DROP>(p, bwd, s);
+        case 3: return launch<3, MEM, DROP>(p, bwd, s);
+        case 4: return launch<4, MEM, DROP>(p, bwd, s);
         default: return NRV_ERR_SHAPE;
     }
 }
@@ -664,7 +717,7 @@ NRV_INTERNAL int nrv_attn_gen_fwd(const void* qkv, void* out, float* lse, int B,
     GenParams p = make_params(qkv, nullptr, 0, 0, nullptr, 0, 0, B, N, H, dh, scale);
     p.o = static_cast<bf16_t*>(out);
     p.lse = lse;
-    return launch<false>(p, false, s);
+    return launch_dh<false>(p, false, s);
 }
 
 NRV_INTERNAL int nrv_attn_gen_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws,
@@ -675,7 +728,29 @@ NRV_INTERNAL int nrv_attn_gen_bwd(const void* qkv, const void* out, const void* 
     p.dqkv = static_cast<bf16_t*>(dqkv);
     p.lse = const_cast<float*>(lse);
     p.delta = delta_ws;
-    return launch<false>(p, true, s);
+    return launch_dh<false>(p, true, s);
+}
+
+// attention-weight dropout (nrv_attn_drop_fwd / _bwd of nrv_attn.hip, T > 0): the DROP instantiations
+NRV_INTERNAL int nrv_attn_gen_drop_fwd(const void* qkv, void* out, float* lse, const unsigned long long* seed, unsigned T, float rs,
+                     int B, int N, int H, int dh, float scale, hipStream_t s) {
+    GenParams p = make_params(qkv, nullptr, 0, 0, nullptr, 0, 0, B, N, H, dh, scale);
+    p.o = static_cast<bf16_t*>(out);
+    p.lse = lse;
+    p.seed = seed; p.drop_T = T; p.drop_rs = rs;
+    return launch_dh<false, true>(p, false, s);
+}
+
+NRV_INTERNAL int nrv_attn_gen_drop_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws,
+                     const unsigned long long* seed, unsigned T, float rs, int B, int N, int H, int dh, float scale, hipStream_t s) {
+    GenParams p = make_params(qkv, nullptr, 0, 0, nullptr, 0, 0, B, N, H, dh, scale);
+    p.out = static_cast<const bf16_t*>(out);
+    p.dout = static_cast<const bf16_t*>(dout);
+    p.dqkv = static_cast<bf16_t*>(dqkv);
+    p.lse = const_cast<float*>(lse);
+    p.delta = delta_ws;
+    p.seed = seed; p.drop_T = T; p.drop_rs = rs;
+    return launch_dh<false, true>(p, true, s);
 }
 
 NRV_INTERNAL int nrv_attn_gen_probs(const void* qkv, const float* lse, float* probs, int B, int N, int H, int dh, float scale, hipStream_t s) {
@@ -698,7 +773,7 @@ extern "C" int nrv_attn_mem_fwd(const void* qkv_bf16, const void* mem_kv_bf16, i
     p.o = static_cast<bf16_t*>(out_bf16);
     p.lse = lse;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return M == 0 && !mask ? launch<false>(p, false, s) : launch<true>(p, false, s);
+    return M == 0 && !mask ? launch_dh<false>(p, false, s) : launch_dh<true>(p, false, s);
 }
 
 extern "C" int nrv_attn_mem_bwd(const void* qkv_bf16, const void* out_bf16, const void* dout_bf16, const float* lse,
@@ -722,7 +797,7 @@ extern "C" int nrv_attn_mem_bwd(const void* qkv_bf16, const void* out_bf16, cons
     p.lse = const_cast<float*>(lse);
     p.delta = delta_ws;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int rc = M == 0 && !mask ? launch<false>(p, true, s) : launch<true>(p, true, s);
+    const int rc = M == 0 && !mask ? launch_dh<false>(p, true, s) : launch_dh<true>(p, true, s);
     if (rc || !dmem_sum_f32) return rc;
     const long long n4 = (long long)M * 2 * H * dh / 4;
     const unsigned gx = (unsigned)((n4 + 255) / 256);

@@ -226,6 +226,12 @@ class BlockMeta:
     mask_source: Optional[object] = None
     # dropout on the attention weights (vit.py:108): composed on the materialised [B,H,N,N] matrix (kernels.attn_composed_fwd), site -(2 + i)
     attn_dropout: float = 0.0
+    # ... or, with `attn_dropout_fused`, inside the fused softmax kernels (kernels.attn_drop_fwd: the mask is a function of a 64-bit
+    # seed and is regenerated in the backward; nothing of size N^2 is written) wherever those kernels apply: no mask_source, no score
+    # bias, not robust, no memories.  `attn_seed_source`: site -> int64 [1] device tensor (tests inject seeds as mask_source injects
+    # masks; default: torch's device generator, one draw per call, graph-safe)
+    attn_dropout_fused: bool = False
+    attn_seed_source: Optional[object] = None
     # additive score bias of ONE call (attention / key-padding masks of the stand-alone MultiheadAttention, utils.py:741-751): fp32,
     # broadcastable to [B, H, N, N], -inf = masked; composed path
     attn_bias: Optional[Tensor] = None
@@ -416,8 +422,10 @@ def _record(qkv: Tensor, att: AttnSaved, B: int, N: int, H: int, dh: int, scale:
 # attention half
 # ----------------------------------------------------------------------------------------------
 class AttnSaved(NamedTuple):
-    """Saved attention state and the path that wrote it: "softmax" (lse), "sinkhorn" (robust=True: lse, scal, and in `saved` the
-    P7 dict of kernels.attn_sinkhorn_fwd) or "composed" (weight dropout / score bias: kernels.ComposedSaved in `saved`)."""
+    """Saved attention state and the path that wrote it: "softmax" (lse), "softmax_drop" (weight dropout inside the fused kernels:
+    lse of the undropped rows, and in `saved` the (seed tensor, p) the backward regenerates the mask from), "sinkhorn" (robust=True:
+    lse, scal, and in `saved` the P7 dict of kernels.attn_sinkhorn_fwd) or "composed" (weight dropout / score bias on the
+    materialised matrix: kernels.ComposedSaved in `saved`)."""
     kind: str
     lse: Optional[Tensor] = None
     scal: Optional[Tensor] = None
@@ -432,6 +440,29 @@ def draw_keep(meta: BlockMeta, site: int, shape, device, p: Optional[float] = No
             raise NrvError(f"mask_source({site}): expected a uint8 mask of shape {tuple(shape)}")
         return m.to(device).contiguous()
     return (torch.rand(shape, device=device) >= (meta.dropout if p is None else p)).to(torch.uint8)
+
+
+FUSED_DROP_DH = (32, 64, 80, 96, 128)          # nrv_attn_drop_fwd's head dims: those of nrv_attn_fwd (row-major)
+
+
+def attn_drop_fused(meta: BlockMeta, adrop) -> bool:
+    """Whether the attention-weight dropout `adrop` of attn_half_fwd runs inside the fused kernels."""
+    return (adrop is not None and meta.attn_dropout_fused and meta.mask_source is None and meta.attn_bias is None
+            and not meta.robust and meta.dim_head in FUSED_DROP_DH)
+
+
+def draw_attn_seeds(meta: BlockMeta, sites, device) -> List[Tensor]:
+    """One int64 [1] seed tensor per site: injected, or slices of ONE draw from torch's device generator."""
+    if meta.attn_seed_source is not None:
+        out = []
+        for site in sites:
+            t = meta.attn_seed_source(site)
+            if t.dtype != torch.int64 or t.numel() != 1:
+                raise NrvError(f"attn_seed_source({site}): expected an int64 tensor of one element")
+            out.append(t.to(device).reshape(1))
+        return out
+    drawn = torch.randint(-2 ** 63, 2 ** 63 - 1, (len(sites),), dtype=torch.int64, device=device)
+    return [drawn[i:i + 1] for i in range(len(sites))]
 
 
 class MemKV(NamedTuple):
@@ -470,10 +501,15 @@ def attn_half_fwd(x: Tensor, B: int, N: int, meta: BlockMeta, ln_w, ln_b, wqkv, 
             mkv = K.gemm_nt(mem16, wqkv_b[H * dh:], out_dtype=torch.bfloat16)
         o, lse = K.attn_mem_fwd(qkv, mkv, B, N, mem.M, H, dh, scale, mem.shared, mem.mask)
         att = AttnSaved("memory", lse, saved=(mem, mem16, mkv))
+    elif attn_drop_fused(meta, adrop):            # weight dropout inside the fused kernels: the mask is regenerated from the seed
+        pa = adrop[2]
+        seed = adrop[3] if len(adrop) > 3 and adrop[3] is not None else draw_attn_seeds(meta, [adrop[1]], x.device)[0]
+        o, lse = K.attn_drop_fwd(qkv, seed, pa, B, N, H, dh, scale)
+        att = AttnSaved("softmax_drop", lse, saved=(seed, pa))
     elif adrop is not None or meta.attn_bias is not None:      # weight dropout / score masks: the composed path (materialised matrix), softmax or Sinkhorn
         pscale, akeep = 1.0, None
         if adrop is not None:
-            pscale, asite, pa = adrop
+            pscale, asite, pa = adrop[:3]
             akeep = draw_keep(meta, asite, (B, H, N, N), x.device, p=pa)
         o, cs = K.attn_composed_fwd(qkv, B, N, H, dh, scale, 3 if meta.robust else 0, akeep, pscale, bias=meta.attn_bias)
         att = AttnSaved("composed", saved=cs)
@@ -531,6 +567,9 @@ def attn_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, B: int,
         dqkv, dmkv = K.attn_mem_bwd(qkv, o, do, att.lse, mkv, B, N, mem.M, H, dh, scale, mem.shared, mem.mask)
     elif att.kind == "composed":
         dqkv = K.attn_composed_bwd(qkv, do, att.saved, B, N, H, dh, scale)
+    elif att.kind == "softmax_drop":
+        seed, pa = att.saved
+        dqkv = K.attn_drop_bwd(qkv, o, do, att.lse, seed, pa, B, N, H, dh, scale)
     elif att.kind == "sinkhorn":
         dqkv = K.attn_sinkhorn_bwd(qkv, do, att.lse, att.scal, B, N, H, dh, scale, saved=att.saved)
     else:
@@ -701,10 +740,13 @@ class EncoderStackFn(torch.autograd.Function):
         pattn = float(meta.attn_dropout)
         if not 0.0 <= pattn < 1.0:
             raise NrvError(f"attention dropout probability {pattn} outside [0, 1)")
+        seeds = [None] * depth
+        if pattn > 0.0 and attn_drop_fused(meta, (None,)):       # fused weight dropout: one draw of seeds for the whole stack
+            seeds = draw_attn_seeds(meta, [-(2 + i) for i in range(depth)], x2.device)
         for i in range(depth):
             p = params[i * PARAMS_PER_LAYER:(i + 1) * PARAMS_PER_LAYER]
             cur, sa = attn_half_fwd(cur, B, N, meta, *p[0:6], residual=True, drop=(scale, 3 * i) if pdrop > 0.0 else None,
-                                    adrop=(1.0 / (1.0 - pattn), -(2 + i), pattn) if pattn > 0.0 else None)
+                                    adrop=(1.0 / (1.0 - pattn), -(2 + i), pattn, seeds[i]) if pattn > 0.0 else None)
             cur, sm = mlp_half_fwd(cur, meta, *p[6:12], residual=True, save=train, drop=(scale, 3 * i + 1) if pdrop > 0.0 else None)
             saved.append((sa, sm) if train else None)
         ctx.meta, ctx.params, ctx.saved_blocks, ctx.shape = meta, params, saved, (B, N, D)

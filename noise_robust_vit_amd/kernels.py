@@ -371,6 +371,58 @@ def attn_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, B: int, N: int
     return dqkv
 
 
+def attn_drop_peff(p: float) -> float:
+    """The probability the fused attention-weight dropout actually uses: T / 2^16 for T = nrv_attn_drop_threshold(p)."""
+    T = _lib.load().nrv_attn_drop_threshold(float(p))
+    check(min(T, 0), "nrv_attn_drop_threshold")
+    return T / 65536.0
+
+
+def _seed64(seed: Tensor, what: str) -> None:
+    _dev(seed, what)
+    if seed.dtype != torch.int64 or seed.numel() != 1:
+        raise NrvError(f"{what}: expected an int64 device tensor of one element, got {seed.dtype} {tuple(seed.shape)}")
+
+
+def attn_drop_fwd(qkv: Tensor, seed: Tensor, p: float, B: int, N: int, H: int, dh: int, scale: float):
+    """attn_fwd with dropout on the attention weights inside the kernel (include/nrv.h, "Attention-weight dropout"): `seed` is an
+    int64 [1] device tensor read when the kernel runs.  -> (out bf16 [B*N, H*dh], lse fp32 [B,H,N] of the undropped rows)."""
+    _bf16(qkv, "qkv"); _seed64(seed, "seed")
+    if not qkv.is_contiguous() or qkv.numel() != B * N * 3 * H * dh:
+        raise NrvError("attn_drop_fwd: qkv must be contiguous [B*N, 3*H*dh]")
+    out = torch.empty(B * N, H * dh, dtype=torch.bfloat16, device=qkv.device)
+    lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
+    lib = _lib.load()
+    _run("attn_drop_fwd", 4.0 * B * H * N * N * dh, 2 * B * N * H * dh * 4,
+         lambda: lib.nrv_attn_drop_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), seed.data_ptr(), float(p), B, N, H, dh,
+                                       float(scale), _stream()),
+         "nrv_attn_drop_fwd")
+    return out, lse
+
+
+def attn_drop_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, seed: Tensor, p: float, B: int, N: int, H: int, dh: int,
+                  scale: float) -> Tensor:
+    _bf16(qkv, "qkv"); _bf16(out, "out"); _bf16(dout, "dout"); _f32(lse, "lse"); _seed64(seed, "seed")
+    if not (qkv.is_contiguous() and out.is_contiguous() and dout.is_contiguous()):
+        raise NrvError("attn_drop_bwd: operands must be contiguous")
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty(B * H * N, dtype=torch.float32, device=qkv.device)
+    lib = _lib.load()
+    _run("attn_drop_bwd", 10.0 * B * H * N * N * dh, 2 * B * N * H * dh * 8,
+         lambda: lib.nrv_attn_drop_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(),
+                                       delta.data_ptr(), seed.data_ptr(), float(p), B, N, H, dh, float(scale), _stream()),
+         "nrv_attn_drop_bwd")
+    return dqkv
+
+
+def attn_drop_mask(seed: Tensor, p: float, B: int, H: int, N: int) -> Tensor:
+    """uint8 [B, H, N, N] keep decisions of attn_drop_fwd / _bwd for this seed and p (tests; a reference for the composed path)."""
+    _seed64(seed, "seed")
+    keep = torch.empty(B, H, N, N, dtype=torch.uint8, device=seed.device)
+    check(_lib.load().nrv_attn_drop_mask(seed.data_ptr(), float(p), keep.data_ptr(), B, H, N, _stream()), "nrv_attn_drop_mask")
+    return keep
+
+
 def attn_probs(qkv: Tensor, lse: Tensor, B: int, N: int, H: int, dh: int, scale: float, layout: int = 0) -> Tensor:
     """fp32 [B, H, N, N] softmax probabilities recomputed from q, k and the saved log-sum-exp (introspection only)."""
     _bf16(qkv, "qkv"); _f32(lse, "lse")

@@ -156,7 +156,8 @@ class MLPBlock(nn.Sequential):
 
 class EncoderBlock(nn.Module):
     def __init__(self, num_heads: int, hidden_dim: int, mlp_dim: int, dropout: float, attention_dropout: float,
-                 norm_layer: Callable[..., nn.Module] = partial(nn.LayerNorm, eps=1e-6), robust=False):
+                 norm_layer: Callable[..., nn.Module] = partial(nn.LayerNorm, eps=1e-6), robust=False,
+                 fused_attention_dropout=False):
         super().__init__()
         self.num_heads = num_heads
         self.ln_1 = norm_layer(hidden_dim)
@@ -165,7 +166,10 @@ class EncoderBlock(nn.Module):
         self.dropout = nn.Dropout(dropout)
         self.ln_2 = norm_layer(hidden_dim)
         self.mlp = MLPBlock(hidden_dim, mlp_dim, dropout)
-        self._meta = BlockMeta(heads=num_heads, dim_head=hidden_dim // num_heads, eps=self.ln_1.eps, robust=bool(robust))
+        # fused_attention_dropout: the weight dropout of vit.py:108 inside the fused softmax kernels (kernels.attn_drop_fwd) instead of
+        # on the composed path's materialised matrix; robust=True stays composed
+        self._meta = BlockMeta(heads=num_heads, dim_head=hidden_dim // num_heads, eps=self.ln_1.eps, robust=bool(robust),
+                               attn_dropout_fused=bool(fused_attention_dropout))
 
     def layer_params(self):
         return ([self.ln_1.weight, self.ln_1.bias] + self.self_attention.attn_params()
@@ -181,17 +185,19 @@ class EncoderBlock(nn.Module):
 class Encoder(nn.Module):
     def __init__(self, seq_length: int, num_layers: int, num_heads: int, hidden_dim: int, mlp_dim: int,
                  dropout: float, attention_dropout: float,
-                 norm_layer: Callable[..., nn.Module] = partial(nn.LayerNorm, eps=1e-6), robust=False):
+                 norm_layer: Callable[..., nn.Module] = partial(nn.LayerNorm, eps=1e-6), robust=False,
+                 fused_attention_dropout=False):
         super().__init__()
         self.pos_embedding = nn.Parameter(torch.empty(1, seq_length, hidden_dim).normal_(std=0.02))
         self.dropout = nn.Dropout(dropout)
         layers: "OrderedDict[str, nn.Module]" = OrderedDict()
         for i in range(num_layers):
             layers[f"encoder_layer_{i}"] = EncoderBlock(num_heads, hidden_dim, mlp_dim, dropout, attention_dropout,
-                                                        norm_layer, robust=robust)
+                                                        norm_layer, robust=robust, fused_attention_dropout=fused_attention_dropout)
         self.layers = nn.Sequential(layers)
         self.ln = norm_layer(hidden_dim)
-        self._meta = BlockMeta(heads=num_heads, dim_head=hidden_dim // num_heads, eps=self.ln.eps, robust=bool(robust))
+        self._meta = BlockMeta(heads=num_heads, dim_head=hidden_dim // num_heads, eps=self.ln.eps, robust=bool(robust),
+                               attn_dropout_fused=bool(fused_attention_dropout))
 
     def attach_grad_sink(self, sink) -> None:
         self._meta.sink = sink
@@ -221,7 +227,7 @@ class VisionTransformer(nn.Module):
                  mlp_dim: int, dropout: float = 0.0, attention_dropout: float = 0.0, num_classes: int = 1000,
                  representation_size: Optional[int] = None,
                  norm_layer: Callable[..., nn.Module] = partial(nn.LayerNorm, eps=1e-6),
-                 conv_stem_configs=None, robust: bool = False):
+                 conv_stem_configs=None, robust: bool = False, fused_attention_dropout: bool = False):
         super().__init__()
         torch._assert(image_size % patch_size == 0, "Input shape indivisible by patch size!")
         if conv_stem_configs is not None:
@@ -229,13 +235,14 @@ class VisionTransformer(nn.Module):
         self.image_size, self.patch_size, self.hidden_dim, self.mlp_dim = image_size, patch_size, hidden_dim, mlp_dim
         self.attention_dropout, self.dropout, self.num_classes = attention_dropout, dropout, num_classes
         self.representation_size, self.norm_layer, self.robust = representation_size, norm_layer, robust
+        self.fused_attention_dropout = bool(fused_attention_dropout)
 
         self.conv_proj = nn.Conv2d(in_channels=3, out_channels=hidden_dim, kernel_size=patch_size, stride=patch_size)
         seq_length = (image_size // patch_size) ** 2
         self.class_token = nn.Parameter(torch.zeros(1, 1, hidden_dim))
         seq_length += 1
         self.encoder = Encoder(seq_length, num_layers, num_heads, hidden_dim, mlp_dim, dropout, attention_dropout,
-                               norm_layer, robust=robust)
+                               norm_layer, robust=robust, fused_attention_dropout=fused_attention_dropout)
         self.seq_length = seq_length
 
         heads_layers: "OrderedDict[str, nn.Module]" = OrderedDict()

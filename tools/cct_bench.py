@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """CCT training-step throughput (fwd + CE + bwd + clip + AdamW through train.Trainer) for CCT-7/3x1 at 32 px (256 tokens),
 CCT-14/7x2 at 224 px (196 tokens) and CCT-7/7x1 at 224 px (3136 tokens): softmax and robust, attention dropout 0.1 (the
-reference's default: the composed path) and 0.0 (the fused kernels), eager and captured (Trainer.capture).  For comparison, at
+reference's default: the composed path) and 0.0 (the fused kernels), eager and captured (Trainer.capture); `--fused-adrop` adds, beside
+every softmax configuration with attention dropout > 0, the same one with fused_attention_dropout=True (the dropout inside the fused
+kernels).  For comparison, at
 one batch size, the fp32 restatement tests/cct_ref.py run eagerly under bf16 autocast on the same GPU (forward + backward + clip
 + torch AdamW, without attention dropout and drop path: less work than the HIP leg does) in a process of its own that launches
 no HIP kernel of the library.  `--profile` times every C-ABI launch of one eager step with HIP events (kernels.LaunchProfile) and
@@ -10,6 +12,7 @@ in a child process of its own under a time limit, and the run stops at the first
 
     python tools/cct_bench.py [--models 7_3x1_32 ...] [--batches 64 256] [--adrop 0.1 0.0] [--steps 10] [--warmup 3] [--no-eager]
                               [--eager-batch 64] [--chunk 64] [--no-capture] [--no-robust] [--limit 300] [--profile MODEL BATCH]
+                              [--fused-adrop]
 """
 import argparse
 import json
@@ -43,22 +46,22 @@ def _time(fn, steps, warmup):
     return (time.perf_counter() - t0) / steps
 
 
-def _build(name, robust, adrop):
+def _build(name, robust, adrop, fused=False):
     from noise_robust_vit_amd import cct
     fn, kw, size = MODELS[name]
-    return getattr(cct, fn)(robust=robust, attention_dropout=adrop, **kw), size
+    return getattr(cct, fn)(robust=robust, attention_dropout=adrop, fused_attention_dropout=fused, **kw), size
 
 
-def one(name, B, robust, adrop, steps, warmup, no_capture=False):
+def one(name, B, robust, adrop, steps, warmup, no_capture=False, fused=False):
     """The HIP legs of one configuration: Trainer.step eager, then captured.  A batch that does not fit is reported, not an error."""
     import torch
     from noise_robust_vit_amd.train import Trainer, TrainConfig
     dev = torch.device("cuda:0")
-    tag = {"model": name, "batch": B, "robust": robust, "attention_dropout": adrop}
+    tag = {"model": name, "batch": B, "robust": robust, "attention_dropout": adrop, "fused_attention_dropout": fused}
     try:
         for captured in ((False,) if no_capture else (False, True)):
             torch.manual_seed(0)
-            m, size = _build(name, robust, adrop)
+            m, size = _build(name, robust, adrop, fused)
             m = m.to(dev).train()
             x = torch.randn(B, 3, size, size, device=dev)
             y = torch.randint(0, 100, (B,), device=dev)
@@ -74,14 +77,14 @@ def one(name, B, robust, adrop, steps, warmup, no_capture=False):
         print(json.dumps(dict(tag, fits=False, note="out of memory")), flush=True)
 
 
-def profile(name, B):
-    """One eager forward + backward at attention_dropout 0 with every launch timed alone: per kernel class launches, ms, the
+def profile(name, B, fused=False):
+    """One eager forward + backward at attention_dropout 0 (with `fused`: 0.1 inside the fused kernels) with every launch timed alone: per kernel class launches, ms, the
     bytes the wrapper computes from the shapes, GB/s and the share of the HBM peak."""
     import torch
     from noise_robust_vit_amd import kernels as K
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    m, size = _build(name, False, 0.0)
+    m, size = _build(name, False, 0.1 if fused else 0.0, fused)
     m = m.to(dev).train()
     x = torch.randn(B, 3, size, size, device=dev)
     y = torch.randint(0, 100, (B,), device=dev)
@@ -151,16 +154,18 @@ def main():
     ap.add_argument("--limit", type=int, default=300, help="seconds per configuration")
     ap.add_argument("--one", nargs=4, metavar=("MODEL", "BATCH", "ROBUST", "ADROP"), help="run one configuration in this process")
     ap.add_argument("--one-eager", nargs=3, metavar=("MODEL", "BATCH", "ROBUST"), help="run one restatement in this process")
+    ap.add_argument("--fused-adrop", action="store_true", help="add the fused_attention_dropout=True configurations (softmax, dropout > 0)")
+    ap.add_argument("--fused", action="store_true", help="with --one / --profile: fused_attention_dropout=True")
     ap.add_argument("--profile", nargs=2, metavar=("MODEL", "BATCH"), help="per-launch timing of one eager step in this process")
     a = ap.parse_args()
     if a.one:
-        one(a.one[0], int(a.one[1]), a.one[2] == "1", float(a.one[3]), a.steps, a.warmup, a.no_capture)
+        one(a.one[0], int(a.one[1]), a.one[2] == "1", float(a.one[3]), a.steps, a.warmup, a.no_capture, a.fused)
         return 0
     if a.one_eager:
         restatement(a.one_eager[0], int(a.one_eager[1]), a.one_eager[2] == "1", a.steps, a.chunk)
         return 0
     if a.profile:
-        profile(a.profile[0], int(a.profile[1]))
+        profile(a.profile[0], int(a.profile[1]), a.fused)
         return 0
     base = [sys.executable, os.path.abspath(__file__), "--steps", str(a.steps), "--warmup", str(a.warmup), "--chunk", str(a.chunk)]
     for name in a.models:
@@ -168,6 +173,9 @@ def main():
             for robust in ((False,) if a.no_robust else (False, True)):
                 cmds = [base + ["--one", name, str(B), "1" if robust else "0", str(p)] + (["--no-capture"] if a.no_capture else [])
                         for p in a.adrop]
+                if a.fused_adrop and not robust:
+                    cmds += [base + ["--one", name, str(B), "0", str(p), "--fused"] + (["--no-capture"] if a.no_capture else [])
+                             for p in a.adrop if p > 0.0]
                 if not a.no_eager and B == a.eager_batch:
                     cmds.append(base + ["--one-eager", name, str(B), "1" if robust else "0"])
                 for cmd in cmds:

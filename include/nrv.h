@@ -794,6 +794,49 @@ size_t nrv_seqpool_bwd_workspace(int B, int D);
 int nrv_seqpool_bwd(const float* dout, const float* y, const float* a, const float* w, float* dy, float* da, float* dbias,
                     void* workspace, size_t workspace_bytes, int B, int n, int D, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Twins-SVT (added to ABI 19 without changing an existing prototype, so the version number stays; twins_svt.py).
+ *
+ * Sub-sampled global attention (GlobalAttention, twins_svt.py:123-154): every query of a map against the few pooled keys of
+ * its sample.  q: bf16 row-major view [B*Nq, ldq] whose first column is head 0's q, head h at column h*dh; k, v: bf16 views
+ * [B*Nk, ldk] / [B*Nk, ldv], head-major likewise (separate pointers: the two halves of one to_kv output work).
+ *   nrv_subattn_fwd  : out bf16 [B*Nq, H*dh] = softmax(scale q k^T) v, lse fp32 [B, H, Nq].  bf16 operands, fp32 accumulation;
+ *                      e = exp(scale s - max) is rounded to bf16 once for the product with v, the row sum adds the unrounded e,
+ *                      one rounding on the store.
+ *   nrv_subattn_bwd  : from q, k, v, dout bf16 [B*Nq, H*dh] and lse (NOT out: with every key of a row on chip
+ *                      dS = P (dP - rowsum(P dP)) needs no saved delta).  dq laid out like q; dk / dv laid out like k / v.
+ *                      P and dS are rounded to bf16 once, before dV = P^T dO and dQ = scale dS K, dK = scale dS^T Q.  dK and dV
+ *                      are accumulated in fp32 over a workgroup's chunk of query rows, one fp32 partial per chunk goes to the
+ *                      workspace (nrv_subattn_bwd_workspace bytes) and a second kernel adds the chunks in index order.  No
+ *                      atomics; the chunk length is a constant of the library, so reruns and machines agree bit for bit.
+ *   nrv_subattn_plan : chunk = query rows per workgroup, chunks = ceil(Nq / chunk), nk_pad = keys staged on chip (Nk rounded
+ *                      up to 32; keys >= Nk are masked, never read).  Read-only, needs no GPU.
+ *   dh in {32, 64}, 1 <= Nk <= 128, Nq >= 1, B, H in [1, 65535], ld* >= H*dh and ld* % 8 == 0; else NRV_ERR_SHAPE.  Shapes are
+ *   checked first, then pointers (NRV_ERR_NULL), then the workspace size, then the 16-byte alignment of every bf16 base and the
+ *   workspace, all before any launch.
+ * PEG (twins_svt.py:81-87): x + Conv2d(C, C, ks, padding ks / 2, groups = C)(x) on token-major rows of the fp32 residual
+ * stream [B*H*W, C].  w fp32 [C, ks*ks] (the Conv2d weight [C, 1, ks, ks] viewed flat), bias fp32 [C].
+ *   nrv_peg_fwd : out fp32 = x + bias[c] + sum_t w[c, t] x(p + off_t), t = ky * ks + kx ascending, taps outside the plane skipped.
+ *   nrv_peg_bwd : dx fp32 = dy + the gather of dy through the flipped taps; dw fp32 [C, ks*ks] and dbias fp32 [C] = per-sample
+ *                 partials (tokens in row-major order) summed over the samples in index order.  No atomics.
+ *                 workspace: nrv_peg_bwd_workspace(B, H, W, C, ks) bytes (the partials).
+ *   ks in {3, 5, 7}, C % 8 == 0, B <= 65535, H * W <= 2^24, any H, W >= 1; else NRV_ERR_SHAPE; then NRV_ERR_NULL, the workspace
+ *   size and the 16-byte alignment of x / out / dy / dx / bias / workspace.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct { int chunk, chunks, nk_pad; } nrv_subattn_plan_t;
+int nrv_subattn_plan(int Nq, int Nk, int dh, nrv_subattn_plan_t* plan);
+int nrv_subattn_fwd(const void* q_bf16, int64_t ldq, const void* k_bf16, int64_t ldk, const void* v_bf16, int64_t ldv,
+                    void* out_bf16, float* lse, int B, int H, int Nq, int Nk, int dh, float scale, void* stream);
+size_t nrv_subattn_bwd_workspace(int B, int H, int Nq, int Nk, int dh);
+int nrv_subattn_bwd(const void* q_bf16, int64_t ldq, const void* k_bf16, int64_t ldk, const void* v_bf16, int64_t ldv,
+                    const void* dout_bf16, const float* lse, void* dq_bf16, void* dk_bf16, void* dv_bf16, void* workspace,
+                    size_t workspace_bytes, int B, int H, int Nq, int Nk, int dh, float scale, void* stream);
+int nrv_peg_fwd(const float* x_f32, const float* w, const float* bias, float* out_f32, int B, int H, int W, int C, int ks,
+                void* stream);
+size_t nrv_peg_bwd_workspace(int B, int H, int W, int C, int ks);
+int nrv_peg_bwd(const float* x_f32, const float* w, const float* dy_f32, float* dx_f32, float* dw, float* dbias, void* workspace,
+                size_t workspace_bytes, int B, int H, int W, int C, int ks, void* stream);
+
 /* CUs the GEMM launches leave free (process-wide; default 0; returns the previous value, or a negative error code when n is
  * negative or leaves fewer than 8 CUs).  The NT GEMM is persistent (one workgroup per CU for the whole launch) and the TN
  * GEMM sizes its token splits to one round of the CUs: with a collective's kernels resident on some CUs (RCCL all-reduce

@@ -22,6 +22,8 @@ from . import deepvit  # noqa: F401
 from .deepvit import DeepViT  # noqa: F401
 from . import cct  # noqa: F401
 from .cct import CCT  # noqa: F401
+from . import twins_svt  # noqa: F401
+from .twins_svt import TwinsSVT  # noqa: F401
 
 
 def invalidate_weight_cache() -> None:
@@ -36,4 +38,4 @@ __all__ = ["invalidate_weight_cache", "SimpleViT", "Attention", "FeedForward", "
            "VisionTransformer", "vit_s_16", "vit_b_16", "vit_b_32", "vit_l_16", "vit_l_32",
            "SwinTransformer", "swin_t", "swin_s", "swin_b", "levit", "patch_convnet", "cait",
            "t2t", "T2TViT", "RearrangeImage", "conv_output_size", "rvt", "RvT", "pit", "PiT",
-           "deepvit", "DeepViT", "cct", "CCT"]
+           "deepvit", "DeepViT", "cct", "CCT", "twins_svt", "TwinsSVT"]

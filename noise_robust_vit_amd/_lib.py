@@ -46,6 +46,11 @@ class BgemmPlan(ctypes.Structure):
                 ("blocks", ctypes.c_longlong)]
 
 
+class SubattnPlan(ctypes.Structure):
+    """include/nrv.h `nrv_subattn_plan_t`: how nrv_subattn_fwd / _bwd split the query rows and pad the keys."""
+    _fields_ = [("chunk", c_int), ("chunks", c_int), ("nk_pad", c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/nrv.h declares (tests/test_abi.py checks the two agree)
 SIGNATURES = {
     "nrv_abi_version": (c_int, []),
@@ -201,6 +206,16 @@ SIGNATURES = {
     "nrv_seqpool_bwd_workspace": (c_size_t, [c_int, c_int]),
     "nrv_seqpool_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
                                 c_int, c_void_p]),
+    "nrv_subattn_plan": (c_int, [c_int, c_int, c_int, c_void_p]),
+    "nrv_subattn_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                c_int, c_float, c_void_p]),
+    "nrv_subattn_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "nrv_subattn_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "nrv_peg_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "nrv_peg_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "nrv_peg_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int,
+                            c_int, c_void_p]),
     "nrv_set_reserved_cus": (c_int, [c_int]),
     "nrv_probe": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p]),
 }

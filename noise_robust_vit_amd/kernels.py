@@ -2031,3 +2031,122 @@ def seqpool_bwd(dout: Tensor, y: Tensor, a: Tensor, w: Tensor, B: int, n: int, d
          lambda: lib.nrv_seqpool_bwd(dout.data_ptr(), y.data_ptr(), a.data_ptr(), w.data_ptr(), dy.data_ptr(), da.data_ptr(), db.data_ptr(),
                                      ws.data_ptr(), ws.numel(), B, n, D, _stream()), "nrv_seqpool_bwd")
     return dy, da, db
+
+
+# ----------------------------------------------------------------------------------------------
+# Twins-SVT (added to ABI 19): sub-sampled global attention with K and V on chip, PEG on the fp32 stream
+# ----------------------------------------------------------------------------------------------
+SUBATTN_MAX_NK = 128             # include/nrv.h nrv_subattn_*: 1 <= Nk <= 128, dh in {32, 64}
+
+
+def subattn_plan(Nq: int, Nk: int, dh: int) -> dict:
+    """How subattn_fwd / _bwd split this shape (include/nrv.h nrv_subattn_plan): query rows per workgroup, chunks per head and
+    the keys staged on chip.  Read-only; needs no GPU.  Raises NrvError where the launch would refuse the shape."""
+    pl = _lib.SubattnPlan()
+    check(_lib.load().nrv_subattn_plan(int(Nq), int(Nk), int(dh), ctypes.addressof(pl)), "nrv_subattn_plan")
+    return {"chunk": pl.chunk, "chunks": pl.chunks, "nk_pad": pl.nk_pad}
+
+
+def _sub_view(t: Tensor, rows: int, width: int, name: str) -> int:
+    _bf16(t, name)
+    if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != rows or t.shape[1] < width:
+        raise NrvError(f"subattn: {name} must be a row-major bf16 [{rows}, >= {width}] view, got {tuple(t.shape)} stride {t.stride()}")
+    return t.stride(0) if rows > 1 else max(t.stride(0), width)
+
+
+def _sub_args(q: Tensor, k: Tensor, v: Tensor, B: int, H: int, Nq: int, Nk: int, dh: int) -> Tuple[int, int, int]:
+    if dh not in (32, 64) or not 1 <= Nk <= SUBATTN_MAX_NK or Nq < 1 or B < 1 or H < 1:
+        raise NrvError(f"subattn: dh {dh} must be 32 or 64, 1 <= Nk <= {SUBATTN_MAX_NK} (got {Nk}), Nq {Nq} >= 1")
+    return _sub_view(q, B * Nq, H * dh, "q"), _sub_view(k, B * Nk, H * dh, "k"), _sub_view(v, B * Nk, H * dh, "v")
+
+
+def subattn_fwd(q: Tensor, k: Tensor, v: Tensor, B: int, H: int, Nq: int, Nk: int, dh: int, scale: float,
+                out: Optional[Tensor] = None, lse: Optional[Tensor] = None):
+    """softmax(scale q k^T) v with the head's K and V on chip (include/nrv.h nrv_subattn_fwd).  q / k / v: bf16 views [B*Nq|Nk, *]
+    whose first column is head 0, head h at column h*dh (column blocks of wider buffers work).  Returns (out bf16 [B*Nq, H*dh],
+    lse fp32 [B, H, Nq])."""
+    ldq, ldk, ldv = _sub_args(q, k, v, B, H, Nq, Nk, dh)
+    out = _out_buffer(out, (B * Nq, H * dh), torch.bfloat16, q.device, "out")
+    lse = _out_buffer(lse, (B, H, Nq), torch.float32, q.device, "lse")
+    _run("subattn_fwd", 4.0 * B * H * Nq * Nk * dh, 2.0 * H * dh * (2 * B * Nq + 2 * B * Nk) + 4.0 * B * H * Nq,
+         lambda: _lib.load().nrv_subattn_fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), lse.data_ptr(),
+                                             B, H, Nq, Nk, dh, float(scale), _stream()),
+         "nrv_subattn_fwd")
+    return out, lse
+
+
+def subattn_bwd(q: Tensor, k: Tensor, v: Tensor, dout: Tensor, lse: Tensor, B: int, H: int, Nq: int, Nk: int, dh: int, scale: float,
+                dq: Optional[Tensor] = None, dk: Optional[Tensor] = None, dv: Optional[Tensor] = None):
+    """(dq, dk, dv) bf16, laid out like q / k / v (given: views with the same row stride; else fresh [rows, H*dh] tensors with the
+    layout of contiguous q / k / v).  Takes lse, not out; deterministic (include/nrv.h nrv_subattn_bwd)."""
+    ldq, ldk, ldv = _sub_args(q, k, v, B, H, Nq, Nk, dh)
+    _bf16(dout, "dout"); _f32(lse, "lse")
+    if tuple(dout.shape) != (B * Nq, H * dh) or not dout.is_contiguous():
+        raise NrvError(f"subattn_bwd: dout must be contiguous [{B * Nq}, {H * dh}], got {tuple(dout.shape)}")
+    if tuple(lse.shape) != (B, H, Nq) or not lse.is_contiguous():
+        raise NrvError(f"subattn_bwd: lse {tuple(lse.shape)} does not belong to this call")
+    grads = []
+    for g, like, rows, ld, name in ((dq, q, B * Nq, ldq, "dq"), (dk, k, B * Nk, ldk, "dk"), (dv, v, B * Nk, ldv, "dv")):
+        if g is None:
+            if ld != H * dh:
+                raise NrvError(f"subattn_bwd: {name[1]} is a view with row stride {ld}; pass {name} as a view of the same layout")
+            g = torch.empty(rows, H * dh, dtype=torch.bfloat16, device=q.device)
+        elif _sub_view(g, rows, H * dh, name) != ld:
+            raise NrvError(f"subattn_bwd: {name} must be laid out like {name[1]} (row stride {ld})")
+        grads.append(g)
+    dq, dk, dv = grads
+    lib = _lib.load()
+    wsb = lib.nrv_subattn_bwd_workspace(B, H, Nq, Nk, dh)
+    ws = _workspace(wsb, q.device)
+    _run("subattn_bwd", 10.0 * B * H * Nq * Nk * dh, 2.0 * H * dh * (4 * B * Nq + 4 * B * Nk) + 4.0 * B * H * Nq + 2.0 * wsb,
+         lambda: lib.nrv_subattn_bwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, dout.data_ptr(), lse.data_ptr(),
+                                     dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(), ws.numel(), B, H, Nq, Nk, dh,
+                                     float(scale), _stream()),
+         "nrv_subattn_bwd")
+    return dq, dk, dv
+
+
+def _peg_args(x: Tensor, w: Tensor, B: int, H: int, W: int, fn: str) -> Tuple[int, int, Tensor]:
+    _f32(x, "x"); _f32(w, "w")
+    if x.dim() != 2 or not x.is_contiguous() or x.shape[0] != B * H * W or x.shape[1] % 8:
+        raise NrvError(f"{fn}: x must be contiguous fp32 [{B * H * W}, C] with C % 8 == 0, got {tuple(x.shape)}")
+    C = x.shape[1]
+    if w.numel() % C:
+        raise NrvError(f"{fn}: w has {w.numel()} elements for {C} channels")
+    kk = w.numel() // C
+    ks = int(round(kk ** 0.5))
+    if ks * ks != kk or ks not in (3, 5, 7):
+        raise NrvError(f"{fn}: w must hold ks*ks taps per channel with ks in (3, 5, 7), got {kk}")
+    return C, ks, w.reshape(C, kk).contiguous()
+
+
+def peg_fwd(x: Tensor, w: Tensor, bias: Tensor, B: int, H: int, W: int, out: Optional[Tensor] = None) -> Tensor:
+    """out fp32 = x + bias + depthwise ks x ks conv(x) (stride 1, zero padding ks / 2) on the fp32 rows x [B*H*W, C]; w fp32
+    [C, 1, ks, ks] or [C, ks*ks], bias fp32 [C] (include/nrv.h nrv_peg_fwd)."""
+    C, ks, w2 = _peg_args(x, w, B, H, W, "peg_fwd")
+    _f32(bias, "bias")
+    if bias.numel() != C or not bias.is_contiguous():
+        raise NrvError(f"peg_fwd: bias must be contiguous [{C}]")
+    out = _out_buffer(out, x.shape, torch.float32, x.device, "out")
+    _run("peg_fwd", 2.0 * ks * ks * x.numel(), 8 * x.numel(),
+         lambda: _lib.load().nrv_peg_fwd(x.data_ptr(), w2.data_ptr(), bias.data_ptr(), out.data_ptr(), B, H, W, C, ks, _stream()),
+         "nrv_peg_fwd")
+    return out
+
+
+def peg_bwd(x: Tensor, w: Tensor, dy: Tensor, B: int, H: int, W: int, dx: Optional[Tensor] = None, dw: Optional[Tensor] = None,
+            dbias: Optional[Tensor] = None):
+    """(dx fp32 like x, dw fp32 of w's shape, dbias fp32 [C]) from dy fp32 like x (include/nrv.h nrv_peg_bwd)."""
+    C, ks, w2 = _peg_args(x, w, B, H, W, "peg_bwd")
+    _f32(dy, "dy")
+    if dy.shape != x.shape or not dy.is_contiguous():
+        raise NrvError(f"peg_bwd: dy must be contiguous with x's shape {tuple(x.shape)}, got {tuple(dy.shape)}")
+    dx = _out_buffer(dx, x.shape, torch.float32, x.device, "dx")
+    dw = _out_buffer(dw, (C, ks * ks), torch.float32, x.device, "dw")
+    db = _out_buffer(dbias, (C,), torch.float32, x.device, "dbias")
+    lib = _lib.load()
+    ws = _workspace(lib.nrv_peg_bwd_workspace(B, H, W, C, ks), x.device)
+    _run("peg_bwd", 4.0 * ks * ks * x.numel(), 16 * x.numel(),
+         lambda: lib.nrv_peg_bwd(x.data_ptr(), w2.data_ptr(), dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
+                                 ws.numel(), B, H, W, C, ks, _stream()), "nrv_peg_bwd")
+    return dx, dw.reshape(w.shape), db

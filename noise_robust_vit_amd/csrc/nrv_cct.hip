@@ -5,12 +5,12 @@
 //     and a backward that takes an fp32 gradient;
 //   * sequence pooling, softmax_n(y a + bias) . y (cct.py:286-288), forward and backward.
 // All of it is memory-bound: 16-byte accesses, fp32 arithmetic in registers, every sum in a fixed order (no atomics), so reruns
-// are bit-identical.  Grids are exact (one work item per thread, wave or workgroup; no capped grid-stride loop).
+// are bit-identical: the per-workgroup partials of dgamma / dbeta and the per-sample partials of the pooling's da / dbias are
+// added by reduce_rows_kernel (nrv_rows.hpp).  Grids are exact (one work item per thread, wave or workgroup; no capped
+// grid-stride loop).
 #include "nrv_rows.hpp"
 
 namespace {
-
-constexpr long long CCT_MAX_BLOCKS = 0x7fffffffll;
 
 // ---------------------------------------------------------------------------------------------
 // ReLU + max pool
@@ -123,7 +123,7 @@ bool maxpool_shape_ok(int B, int H, int W, int C, int pk, int ps, int pp) {
     if (!(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && C <= (1 << 20) && (long long)H * W <= (1ll << 24))) return false;
     if (H + 2 * pp < pk || W + 2 * pp < pk) return false;
     const long long rows = (long long)B * H * W;
-    return rows * C <= (1ll << 40) && nrv_cdiv(rows * (C / 8), 256) <= CCT_MAX_BLOCKS;
+    return rows * C <= (1ll << 40) && nrv_cdiv(rows * (C / 8), 256) <= NRV_MAX_BLOCKS;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -253,38 +253,16 @@ __global__ __launch_bounds__(256) void lnf_bwd_kernel(const float* __restrict__ 
     }
 }
 
-// out[c] = sum_p partial[p][c] over P partial rows of `ncols` floats: 16 columns x 64 row lanes per workgroup, lane r adds rows
-// r, r + 64, ... in order, then the 64 lane sums are added in order.  Columns < split go to out0, the rest to out1.
-constexpr int CRR_COLS = 16, CRR_LANES = 64;
-__global__ __launch_bounds__(CRR_COLS * CRR_LANES) void cct_reduce_rows_kernel(const float* __restrict__ partial, long long P, int ncols,
-                                                                               float* __restrict__ out0, float* __restrict__ out1, int split) {
-    __shared__ float red[CRR_LANES][CRR_COLS + 1];
-    const int cl = threadIdx.x % CRR_COLS, rl = threadIdx.x / CRR_COLS;
-    const int c = blockIdx.x * CRR_COLS + cl;
-    float s = 0.f;
-    if (c < ncols)
-        for (long long p = rl; p < P; p += CRR_LANES) s += partial[p * ncols + c];
-    red[rl][cl] = s;
-    __syncthreads();
-    if (rl == 0 && c < ncols) {
-        float t = 0.f;
-#pragma unroll 8
-        for (int k = 0; k < CRR_LANES; ++k) t += red[k][cl];
-        if (c < split) out0[c] = t;
-        else out1[c - split] = t;
-    }
-}
-
 // rows one wave of the backward walks: 8, or more so that the launch has at most 4096 waves (1024 workgroups: that many
-// partial rows of dgamma / dbeta)
+// partial rows of dgamma / dbeta, an int for reduce_rows_kernel)
 int lnf_rpw(long long rows) {
     const long long r = nrv_cdiv(rows, 4096);
     return (int)(r < LNF_ROWS_PER_WAVE ? LNF_ROWS_PER_WAVE : (r > 0x7fffffff ? 0x7fffffff : r));
 }
-long long lnf_bwd_blocks(long long rows) { return nrv_cdiv(nrv_cdiv(rows, lnf_rpw(rows)), 4); }
+int lnf_bwd_blocks(long long rows) { return (int)nrv_cdiv(nrv_cdiv(rows, lnf_rpw(rows)), 4); }
 
 bool lnf_shape_ok(long long rows, int dim) {
-    return rows >= 1 && dim >= 8 && dim % 8 == 0 && dim <= 4096 && rows <= (1ll << 40) / dim && nrv_cdiv(rows, 4) <= CCT_MAX_BLOCKS;
+    return rows >= 1 && dim >= 8 && dim % 8 == 0 && dim <= 4096 && rows <= (1ll << 40) / dim && nrv_cdiv(rows, 4) <= NRV_MAX_BLOCKS;
 }
 int lnf_maxj(int dim) {
     const int chunks = (dim / 4 + 63) / 64;
@@ -459,7 +437,7 @@ extern "C" int nrv_layernorm_f32_bwd(const float* dy, const float* x, const floa
         !nrv_aligned16(workspace))
         return NRV_ERR_ALIGN;
     const int rpw = lnf_rpw(rows);
-    const long long blocks = lnf_bwd_blocks(rows);
+    const int blocks = lnf_bwd_blocks(rows);
     const dim3 grid((unsigned)blocks);
     const size_t lds = (size_t)4 * dim * 4;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -473,8 +451,8 @@ extern "C" int nrv_layernorm_f32_bwd(const float* dy, const float* x, const floa
         default: hipLaunchKernelGGL(lnf_bwd_kernel<16>, grid, dim3(256), lds, st, dy, x, gamma, mean, rstd, dx_f32, dx16, part, rows, dim, rpw); break;
     }
     NRV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(cct_reduce_rows_kernel, dim3((unsigned)nrv_cdiv(2 * dim, CRR_COLS)), dim3(CRR_COLS * CRR_LANES), 0, st, part, blocks, 2 * dim,
-                       dgamma, dbeta, dim);
+    hipLaunchKernelGGL(reduce_rows_kernel<RR_COLS * RR_LANES>, dim3((unsigned)nrv_cdiv(2 * dim, RR_COLS)), dim3(RR_COLS * RR_LANES), 0, st, part,
+                       blocks, 2 * dim, dgamma, dbeta, dim, 0.f);
     NRV_CHECK_LAUNCH();
     return 0;
 }
@@ -504,10 +482,11 @@ extern "C" int nrv_seqpool_bwd(const float* dout, const float* y, const float* a
     hipLaunchKernelGGL(seqpool_bwd_kernel, dim3((unsigned)B), dim3(256), 0, st, dout, y, a, w, dy, part, B, n, D);
     NRV_CHECK_LAUNCH();
     // da[c] = sum_b part[b][c], dbias = sum_b part[B * D + b]: lane r of 64 adds samples r, r + 64, ..., then the lanes in order
-    hipLaunchKernelGGL(cct_reduce_rows_kernel, dim3((unsigned)nrv_cdiv(D, CRR_COLS)), dim3(CRR_COLS * CRR_LANES), 0, st, part, (long long)B, D, da,
-                       da, D);
+    hipLaunchKernelGGL(reduce_rows_kernel<RR_COLS * RR_LANES>, dim3((unsigned)nrv_cdiv(D, RR_COLS)), dim3(RR_COLS * RR_LANES), 0, st, part, B, D, da,
+                       da, D, 0.f);
     NRV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(cct_reduce_rows_kernel, dim3(1), dim3(CRR_COLS * CRR_LANES), 0, st, part + (long long)B * D, (long long)B, 1, dbias, dbias, 1);
+    hipLaunchKernelGGL(reduce_rows_kernel<RR_COLS * RR_LANES>, dim3(1), dim3(RR_COLS * RR_LANES), 0, st, part + (long long)B * D, B, 1, dbias, dbias,
+                       1, 0.f);
     NRV_CHECK_LAUNCH();
     return 0;
 }

@@ -216,5 +216,15 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
         if (e__ != hipSuccess) return (int)e__;     \
     } while (0)
 
+// CALL with constexpr int KS = ks, one of the depthwise kernel sizes 3 / 5 / 7 that the shape checks admit
+#define NRV_DISPATCH_KS(ks, CALL)                            \
+    do {                                                     \
+        if ((ks) == 3) { constexpr int KS = 3; CALL; }       \
+        else if ((ks) == 5) { constexpr int KS = 5; CALL; }  \
+        else { constexpr int KS = 7; CALL; }                 \
+    } while (0)
+
+constexpr long long NRV_MAX_BLOCKS = 0x7fffffffll;      // workgroups in gridDim.x, at most: the exact grids are checked against it
+
 static inline bool nrv_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int64_t nrv_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

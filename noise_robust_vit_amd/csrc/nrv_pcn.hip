@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void dw_fwd_kernel(const bf16_t* __restrict__ 
 }
 
 // backward, pass 1: dd = (dg s[b] + dmean[b] / HW) gelu'(pre), pre recomputed from a; fp32 dd to the workspace; per-(sample,
-// channel) partials of dW (9 taps) and db, reduced over the row groups in order.
+// channel) partials of dW (9 taps) and db, reduced over the row groups in order: part[(b * 10 + t) * C + c], db at t = 9.
 __global__ __launch_bounds__(256) void dw_bwd_dd_kernel(const bf16_t* __restrict__ a, const float* __restrict__ w, const float* __restrict__ bias,
                                                         const bf16_t* __restrict__ dg, const float* __restrict__ s, const float* __restrict__ dmean,
                                                         float inv_hw, float* __restrict__ dd, float* __restrict__ part, int H, int W, int C) {
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void dw_bwd_dd_kernel(const bf16_t* __restrict
         if (threadIdx.x < DW_CB && blockIdx.x * DW_CB + (int)threadIdx.x < C) {
             float v = 0.f;
             for (int r = 0; r < DW_RG; ++r) v += red[r][threadIdx.x];
-            part[((long long)b * C + blockIdx.x * DW_CB + threadIdx.x) * 10 + t] = v;
+            part[((long long)b * 10 + t) * C + blockIdx.x * DW_CB + threadIdx.x] = v;
         }
         __syncthreads();
     }
@@ -176,17 +176,7 @@ __global__ __launch_bounds__(256) void dw_bwd_da_kernel(const float* __restrict_
     }
 }
 
-// backward, pass 3: dW [C, 9] and db [C] = the per-sample partials summed over the batch in order
-__global__ __launch_bounds__(256) void dw_bwd_wred_kernel(const float* __restrict__ part, float* __restrict__ dw, float* __restrict__ db,
-                                                          int B, int C) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= C * 10) return;
-    const int c = i / 10, t = i - c * 10;
-    float v = 0.f;
-    for (int b = 0; b < B; ++b) v += part[((long long)b * C + c) * 10 + t];
-    if (t < 9) dw[c * 9 + t] = v;
-    else db[c] = v;
-}
+// backward, pass 3: dW [C, 9] and db [C] = the per-sample partials summed over the batch in order (tap_wred_kernel, nrv_rows.hpp)
 
 // ---------------------------------------------------------------------------------------------
 // squeeze-and-excitation (utils.py:1148-1184)
@@ -346,7 +336,8 @@ __global__ __launch_bounds__(256) void ls_add_kernel(const float* __restrict__ x
 
 constexpr int LS_ROWS = 128;     // rows per partial
 
-// dz = bf16(dy f gamma); partial[chunk, c] = sum over the chunk's rows of dy f y, 4 row lanes reduced in order
+// dz = bf16(dy f gamma); partial[chunk, c] = sum over the chunk's rows of dy f y, 4 row lanes reduced in order; dgamma = the
+// chunks added in index order (sum_rows_kernel, nrv_rows.hpp)
 __global__ __launch_bounds__(256) void ls_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ gamma,
                                                      const float* __restrict__ keep, float inv_surv, bf16_t* __restrict__ dz,
                                                      float* __restrict__ part, long long rows, long long rps, int C) {
@@ -369,14 +360,6 @@ __global__ __launch_bounds__(256) void ls_bwd_kernel(const float* __restrict__ d
     red[rl][lc] = acc;
     __syncthreads();
     if (threadIdx.x < 64 && c < C) part[(long long)blockIdx.y * C + c] = ((red[0][lc] + red[1][lc]) + red[2][lc]) + red[3][lc];
-}
-
-__global__ __launch_bounds__(256) void ls_red_kernel(const float* __restrict__ part, float* __restrict__ dgamma, int chunks, int C) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    float v = 0.f;
-    for (int k = 0; k < chunks; ++k) v += part[(long long)k * C + c];
-    dgamma[c] = v;
 }
 
 // out = bf16(dx gelu'(stream))
@@ -615,7 +598,8 @@ extern "C" int nrv_dwconv3x3_bwd(const void* a, const float* w, const float* bia
     hipLaunchKernelGGL(dw_bwd_da_kernel, dim3(grid_for(n4, 256, PCN_GRID_CAP)), dim3(256), 0, st, dd, w, gelu_stream, gelu_dtype,
                        static_cast<bf16_t*>(da_bf16), n4, H, W, C);
     NRV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dw_bwd_wred_kernel, dim3(grid_for((long long)C * 10, 256, PCN_GRID_CAP)), dim3(256), 0, st, part, dw, db, B, C);
+    // an exact grid: the reducer has no stride loop and dw_shape_ok does not bound C (10 C / 256 fits gridDim.x for any int C)
+    hipLaunchKernelGGL(tap_wred_kernel<256>, dim3((unsigned)nrv_cdiv(10ll * C, 256)), dim3(256), 0, st, part, dw, db, B, C, 9);
     NRV_CHECK_LAUNCH();
     return 0;
 }
@@ -708,7 +692,7 @@ extern "C" int nrv_ls_bwd(const float* dy, const float* y, const float* gamma, c
                        keep ? 1.0f / survival : 1.0f, static_cast<bf16_t*>(dz_bf16), part, (long long)rows,
                        keep ? (long long)rows_per_sample : 1ll, C);
     NRV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ls_red_kernel, dim3((unsigned)nrv_cdiv(C, 256)), dim3(256), 0, st, part, dgamma, chunks, C);
+    hipLaunchKernelGGL(sum_rows_kernel<256>, dim3((unsigned)nrv_cdiv(C, 256)), dim3(256), 0, st, part, chunks, C, dgamma, dgamma, C, 0.f);
     NRV_CHECK_LAUNCH();
     return 0;
 }

@@ -4,8 +4,9 @@
 // output channels (one 16-byte bf16 access); the arithmetic is fp32 in registers with one bf16 rounding on the forward's store.
 // Nothing is staged in LDS: every input is read by 2.25 windows on average, the windows that share it sit in neighbouring
 // lanes of the same or the next workgroup, and a stride-2 tile of T x T outputs would stage (2T + 1)^2 inputs to save those
-// re-reads from the caches.  Every sum runs in a fixed order (no atomics): reruns are bit-identical.  Grids are
-// exact (one work item per thread, no capped grid-stride loop).
+// re-reads from the caches.  Every sum runs in a fixed order (no atomics): reruns are bit-identical; the per-sample
+// partials of dw / dbias are added by tap_wred_kernel (nrv_rows.hpp).  Grids are exact (one work item per thread, no capped
+// grid-stride loop).
 #include "nrv_rows.hpp"
 
 namespace {
@@ -121,27 +122,12 @@ __global__ __launch_bounds__(256) void pool_dw_kernel(const float* __restrict__ 
     part[i] = acc;
 }
 
-// dw [2C, 9] and dbias [2C] = the per-sample partials summed over the samples in index order
-__global__ __launch_bounds__(256) void pool_wred_kernel(const float* __restrict__ part, float* __restrict__ dw, float* __restrict__ dbias, int B,
-                                                        int C2) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int n = 10 * C2;
-    if (i >= n) return;
-    float v = 0.f;
-    for (int b = 0; b < B; ++b) v += part[(long long)b * n + i];
-    const int t = i / C2, o = i - t * C2;
-    if (t < 9) dw[o * 9 + t] = v;
-    else dbias[o] = v;
-}
-
-constexpr long long PIT_MAX_BLOCKS = 0x7fffffffll;
-
 bool pool_shape_ok(int B, int H, int W, int lead, int C) {
     if (!(B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W <= (1ll << 24) && (lead == 0 || lead == 1) && C > 0 && C % 8 == 0 &&
           C <= (1 << 20)))
         return false;
     const long long rows = (long long)B * (lead + (long long)H * W);
-    return rows * C <= (1ll << 40) && nrv_cdiv(rows * (C / 4), 256) <= PIT_MAX_BLOCKS && nrv_cdiv((long long)B * 20 * C, 256) <= PIT_MAX_BLOCKS;
+    return rows * C <= (1ll << 40) && nrv_cdiv(rows * (C / 4), 256) <= NRV_MAX_BLOCKS && nrv_cdiv((long long)B * 20 * C, 256) <= NRV_MAX_BLOCKS;
 }
 
 }  // namespace
@@ -184,7 +170,8 @@ extern "C" int nrv_pool_dwconv_bwd(const float* x_f32, const float* w, const voi
     const long long parts = (long long)B * 20 * C;
     hipLaunchKernelGGL(pool_dw_kernel, dim3((unsigned)nrv_cdiv(parts, 256)), dim3(256), 0, st, x_f32, dout, part, parts, H, W, Ho, Wo, lead, C);
     NRV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pool_wred_kernel, dim3((unsigned)nrv_cdiv(20ll * C, 256)), dim3(256), 0, st, part, dw, dbias, B, 2 * C);
+    // dw [2C, 9] and dbias [2C] = the per-sample partials summed over the samples in index order
+    hipLaunchKernelGGL(tap_wred_kernel<256>, dim3((unsigned)nrv_cdiv(20ll * C, 256)), dim3(256), 0, st, part, dw, dbias, B, 2 * C, 9);
     NRV_CHECK_LAUNCH();
     return 0;
 }

@@ -1,7 +1,8 @@
 // Row helpers shared by the kernels that keep one bf16 row per thread in fp32 registers (biased, window and class attention,
 // the PatchConvNet and batch-norm elementwise kernels): bf16 row <-> fp32 registers, Hardswish, the fixed-order 256-thread
-// LDS tree, the kernel that sums the partials of a table gradient, and the host's grid size.  The MFMA fragment helpers of the
-// ViT attention kernels live in nrv_attn_common.hpp.  Everything here has internal linkage: nothing is an exported symbol.
+// LDS tree, the kernel that sums the partials of a table gradient, the three fixed-order reducers of partial rows that finish
+// every deterministic gradient, and the host's grid size.  The MFMA fragment helpers of the ViT attention kernels live in
+// nrv_attn_common.hpp.  Everything here has internal linkage: nothing is an exported symbol.
 #pragma once
 #include "nrv_common.hpp"
 
@@ -117,6 +118,66 @@ __global__ __launch_bounds__(THREADS) void reduce_partials_kernel(const float* _
     for (int c = threadIdx.x; c < n; c += 256) acc += src[c];
     acc = block_sum_256(acc, red);
     if (threadIdx.x == 0) out[blockIdx.x * sx + blockIdx.y * sy] = acc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The second step of every deterministic gradient: P fp32 partial rows [P, ncols], written by a first kernel, added in one fixed
+// order.  All three are templates for the reason above (THREADS is the workgroup size, fixed per kernel).  The stores share one
+// form: column c goes to out0[c] below `split` and to out1[c - split] from it on, as beta * old + sum when beta != 0.
+// ---------------------------------------------------------------------------------------------
+// out[c] = beta * out[c] + sum_p partial[p][c]  (fixed summation order; tests/norm_ref.py::reduce_rows emulates it)
+// 16 columns x 64 row-lanes per workgroup: lane r adds rows r, r + 64, ... in order, then lane 0 adds the 64 lane sums in order.
+// With ~1000 partial rows and ~1500 columns this gives ~100 workgroups and 16 loads per thread (a 64-column x 16-lane layout
+// left the kernel on 24 CUs with 64 dependent loads per thread: 20 us).  Grid: cdiv(ncols, RR_COLS).
+constexpr int RR_COLS = 16, RR_LANES = 64;
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void reduce_rows_kernel(const float* __restrict__ partial, int P, int ncols,
+                                                              float* __restrict__ out0, float* __restrict__ out1,
+                                                              int split_col, float beta) {
+    static_assert(THREADS == RR_COLS * RR_LANES, "16 columns x 64 row lanes");
+    __shared__ float red[RR_LANES][RR_COLS + 1];
+    const int cl = threadIdx.x % RR_COLS, rl = threadIdx.x / RR_COLS;
+    const int c = blockIdx.x * RR_COLS + cl;
+    float s = 0.f;
+    if (c < ncols)
+        for (int p = rl; p < P; p += RR_LANES) s += partial[(long long)p * ncols + c];
+    red[rl][cl] = s;
+    __syncthreads();
+    if (rl == 0 && c < ncols) {
+        float t = 0.f;
+#pragma unroll 8
+        for (int k = 0; k < RR_LANES; ++k) t += red[k][cl];
+        float* dst = c < split_col ? out0 + c : out1 + (c - split_col);
+        *dst = beta != 0.f ? beta * (*dst) + t : t;
+    }
+}
+
+// The serial form, for few partial rows: one thread per column adds its P partials p = 0 .. P - 1 in index order.
+// Grid: cdiv(ncols, 256), exact.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void sum_rows_kernel(const float* __restrict__ part, int P, int ncols, float* __restrict__ out0,
+                                                           float* __restrict__ out1, int split, float beta) {
+    const long long c = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (c >= ncols) return;
+    float v = 0.f;
+    for (int p = 0; p < P; ++p) v += part[(long long)p * ncols + c];
+    float* dst = c < split ? out0 + c : out1 + (c - split);
+    *dst = beta != 0.f ? beta * (*dst) + v : v;
+}
+
+// Tap gradients of a depthwise convolution: per-sample partials [B][KK + 1][C] (tap t < KK, the bias at t = KK; c fastest), one
+// thread per (t, c) adds the samples b = 0 .. B - 1 in index order; dw [C, KK] and dbias [C].  Grid: cdiv((KK + 1) C, 256), exact.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void tap_wred_kernel(const float* __restrict__ part, float* __restrict__ dw,
+                                                           float* __restrict__ dbias, int B, int C, int KK) {
+    const long long i = (long long)blockIdx.x * THREADS + threadIdx.x;
+    const long long n = (long long)(KK + 1) * C;
+    if (i >= n) return;
+    float v = 0.f;
+    for (int b = 0; b < B; ++b) v += part[b * n + i];
+    const int t = (int)(i / C), c = (int)(i - (long long)t * C);
+    if (t < KK) dw[(long long)c * KK + t] = v;
+    else dbias[c] = v;
 }
 
 // workgroups for `items` work items at `block` per workgroup, at most `cap` (the grid-stride loops take the rest), at least 1

@@ -170,15 +170,6 @@ __global__ __launch_bounds__(256) void dwc_dw_kernel(const bf16_t* __restrict__ 
     }
 }
 
-// dw [C, KK] = the per-sample partials summed over the samples in index order
-__global__ __launch_bounds__(256) void dwc_wred_kernel(const float* __restrict__ part, float* __restrict__ dw, int B, long long n) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float v = 0.f;
-    for (int b = 0; b < B; ++b) v += part[(long long)b * n + i];
-    dw[i] = v;
-}
-
 // ---------------------------------------------------------------------------------------------
 // GEGLU (rvt.py:80-83): u = [x | g] per row, h = x gelu(g).  One thread = 8 columns of a row.
 // ---------------------------------------------------------------------------------------------
@@ -220,8 +211,6 @@ __global__ __launch_bounds__(256) void geglu_bwd_kernel(const bf16_t* __restrict
     store_row(du + r * 2ll * hidden + hidden + c, dg);
 }
 
-constexpr long long RVT_MAX_BLOCKS = 0x7fffffffll;
-
 bool rotary_shape_ok(int B, int N, int lead, int H, int dh, int dr) {
     return B > 0 && N > 0 && (lead == 0 || lead == 1) && N > lead && H > 0 && dh > 0 && dh % 8 == 0 && dr >= 2 && dr % 2 == 0 && dr <= dh &&
            (long long)B * N * 3 * H * dh <= (1ll << 40);
@@ -233,7 +222,7 @@ int rotary_launch(void* qkv, const float* sn, const float* cs, int B, int N, int
     if (!nrv_aligned16(qkv) || !nrv_aligned16(sn) || !nrv_aligned16(cs)) return NRV_ERR_ALIGN;
     const long long items = (long long)B * (N - lead) * 2 * H * ((dr + 7) / 8);
     const long long blocks = nrv_cdiv(items, 256);
-    if (blocks > RVT_MAX_BLOCKS) return NRV_ERR_SHAPE;
+    if (blocks > NRV_MAX_BLOCKS) return NRV_ERR_SHAPE;
     hipLaunchKernelGGL(rotary_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<bf16_t*>(qkv), sn, cs,
                        items, N, lead, H, dh, dr, sgn);
     NRV_CHECK_LAUNCH();
@@ -260,7 +249,7 @@ void dwc_dw_launch(const void* a, const void* dout, float* part, int B, int H, i
 
 bool geglu_shape_ok(long long ld_u, long long rows, int hidden) {
     return rows > 0 && hidden > 0 && hidden % 8 == 0 && ld_u >= 2ll * hidden && ld_u % 8 == 0 && rows <= (1ll << 40) / hidden &&
-           nrv_cdiv(rows * (hidden / 8), 256) <= RVT_MAX_BLOCKS;
+           nrv_cdiv(rows * (hidden / 8), 256) <= NRV_MAX_BLOCKS;
 }
 
 }  // namespace
@@ -283,9 +272,7 @@ extern "C" int nrv_dwconv_fwd(const void* a, const float* w, void* out_bf16, int
     if (!a || !w || !out_bf16) return NRV_ERR_NULL;
     if (!nrv_aligned16(a) || !nrv_aligned16(out_bf16)) return NRV_ERR_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (ks == 3) dwc_conv_launch<3, false>(a, w, out_bf16, B, H, W, lead, C, st);
-    else if (ks == 5) dwc_conv_launch<5, false>(a, w, out_bf16, B, H, W, lead, C, st);
-    else dwc_conv_launch<7, false>(a, w, out_bf16, B, H, W, lead, C, st);
+    NRV_DISPATCH_KS(ks, (dwc_conv_launch<KS, false>(a, w, out_bf16, B, H, W, lead, C, st)));
     NRV_CHECK_LAUNCH();
     return 0;
 }
@@ -303,16 +290,13 @@ extern "C" int nrv_dwconv_bwd(const void* a, const float* w, const void* dout, v
     if (!nrv_aligned16(a) || !nrv_aligned16(dout) || !nrv_aligned16(da_bf16) || !nrv_aligned16(workspace)) return NRV_ERR_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* part = static_cast<float*>(workspace);
-    if (ks == 3) dwc_conv_launch<3, true>(dout, w, da_bf16, B, H, W, lead, C, st);
-    else if (ks == 5) dwc_conv_launch<5, true>(dout, w, da_bf16, B, H, W, lead, C, st);
-    else dwc_conv_launch<7, true>(dout, w, da_bf16, B, H, W, lead, C, st);
+    NRV_DISPATCH_KS(ks, (dwc_conv_launch<KS, true>(dout, w, da_bf16, B, H, W, lead, C, st)));
     NRV_CHECK_LAUNCH();
-    if (ks == 3) dwc_dw_launch<3>(a, dout, part, B, H, W, lead, C, st);
-    else if (ks == 5) dwc_dw_launch<5>(a, dout, part, B, H, W, lead, C, st);
-    else dwc_dw_launch<7>(a, dout, part, B, H, W, lead, C, st);
+    NRV_DISPATCH_KS(ks, (dwc_dw_launch<KS>(a, dout, part, B, H, W, lead, C, st)));
     NRV_CHECK_LAUNCH();
-    const long long n = (long long)C * ks * ks;
-    hipLaunchKernelGGL(dwc_wred_kernel, dim3((unsigned)nrv_cdiv(n, 256)), dim3(256), 0, st, part, dw, B, n);
+    // dw [C, KK] = the per-sample partials [B][C * KK] summed over the samples in index order (C KK <= 65535 * 64 * 49: an int)
+    const int n = C * ks * ks;
+    hipLaunchKernelGGL(sum_rows_kernel<256>, dim3((unsigned)nrv_cdiv(n, 256)), dim3(256), 0, st, part, B, n, dw, dw, n, 0.f);
     NRV_CHECK_LAUNCH();
     return 0;
 }

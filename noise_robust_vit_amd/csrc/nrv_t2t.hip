@@ -4,7 +4,7 @@
 //   LayerNorm over the true width n of rows stored with a stride ld >= n (n = 147, 1323: ks*ks*C is no multiple of 8, the
 //                GEMMs need K % 8 == 0, so the residual stream keeps zero pad columns): statistics over n, pad columns of
 //                y / dx written as zeros.  One wave per row, two passes over the row for mean and centred variance (the
-//                second pass hits L1 / L2).  dgamma / dbeta: per-slab column sums, then a finalize in slab order.
+//                second pass hits L1 / L2).  dgamma / dbeta: per-slab column sums, then sum_rows_kernel (nrv_rows.hpp) in slab order.
 #include "nrv_rows.hpp"
 
 namespace {
@@ -105,19 +105,6 @@ __global__ __launch_bounds__(LNP_THREADS) void ln_pad_dgb_partial_kernel(const b
     part[((long long)s * 2 + 1) * n + j] = db;
 }
 
-__global__ __launch_bounds__(LNP_THREADS) void ln_pad_dgb_final_kernel(const float* __restrict__ part, float* __restrict__ dgamma,
-                                                                       float* __restrict__ dbeta, int slabs, int n, int accumulate) {
-    const int j = blockIdx.x * LNP_THREADS + threadIdx.x;
-    if (j >= n) return;
-    float dg = 0.f, db = 0.f;
-    for (int s = 0; s < slabs; ++s) {
-        dg += part[((long long)s * 2 + 0) * n + j];
-        db += part[((long long)s * 2 + 1) * n + j];
-    }
-    dgamma[j] = accumulate ? dgamma[j] + dg : dg;
-    dbeta[j] = accumulate ? dbeta[j] + db : db;
-}
-
 int lnp_slabs(long long rows) {
     long long s = (rows + LNP_SLAB_ROWS - 1) / LNP_SLAB_ROWS;
     if (s > LNP_MAX_SLABS) s = LNP_MAX_SLABS;
@@ -176,7 +163,9 @@ extern "C" int nrv_layernorm_pad_bwd(const void* dy_bf16, const void* x, int x_d
     if (xf) hipLaunchKernelGGL((ln_pad_dgb_partial_kernel<true>), pg, dim3(LNP_THREADS), 0, s, dy, x, mean, rstd, part, (long long)rows, per, n, (int)ld);
     else hipLaunchKernelGGL((ln_pad_dgb_partial_kernel<false>), pg, dim3(LNP_THREADS), 0, s, dy, x, mean, rstd, part, (long long)rows, per, n, (int)ld);
     NRV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ln_pad_dgb_final_kernel, dim3(pg.x), dim3(LNP_THREADS), 0, s, part, dgamma, dbeta, slabs, n, accumulate);
+    // part is [slabs][2 n], a row = dgamma | dbeta: the slabs added in index order
+    hipLaunchKernelGGL(sum_rows_kernel<256>, dim3((unsigned)nrv_cdiv(2 * n, 256)), dim3(256), 0, s, part, slabs, 2 * n, dgamma, dbeta, n,
+                       accumulate ? 1.0f : 0.0f);
     NRV_CHECK_LAUNCH();
     return 0;
 }

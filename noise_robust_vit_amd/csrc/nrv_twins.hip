@@ -24,7 +24,8 @@
 //             177 VGPRs + 80 AGPRs (one wave per SIMD, which the LDS budget allows anyway); no scratch in either.
 //
 // PEG.  Memory-bound fp32: one thread = (token, 4 channels), the taps through the caches (a 3 x 3 halo re-reads every input 9
-// times from L1 / L2, as nrv_pool_dwconv_* does).  dw / dbias: per-sample partials added in index order.  Grids are exact.
+// times from L1 / L2, as nrv_pool_dwconv_* does).  dw / dbias: per-sample partials added in index order by tap_wred_kernel
+// (nrv_rows.hpp), which the Pool layer's and the 3x3 depthwise convolution's backward share.  Grids are exact.
 #include "nrv_attn_common.hpp"
 #include "nrv_rows.hpp"
 
@@ -436,36 +437,19 @@ __global__ __launch_bounds__(256) void peg_dw_kernel(const float* __restrict__ x
     part[i] = acc;
 }
 
-// dw [C, KK] and dbias [C] = the per-sample partials summed over the samples in index order
-__global__ __launch_bounds__(256) void peg_wred_kernel(const float* __restrict__ part, float* __restrict__ dw, float* __restrict__ dbias, int B,
-                                                       int C, int KK) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int n = (KK + 1) * C;
-    if (i >= n) return;
-    float v = 0.f;
-    for (int b = 0; b < B; ++b) v += part[(long long)b * n + i];
-    const int t = i / C, c = i - t * C;
-    if (t < KK) dw[(long long)c * KK + t] = v;
-    else dbias[c] = v;
-}
-
-constexpr long long TW_MAX_BLOCKS = 0x7fffffffll;
-
 bool peg_shape_ok(int B, int H, int W, int C, int ks) {
     if (!(B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W <= (1ll << 24) && C > 0 && C % 8 == 0 && C <= (1 << 20) &&
           (ks == 3 || ks == 5 || ks == 7)))
         return false;
     const long long rows = (long long)B * H * W;
-    return rows * C <= (1ll << 40) && nrv_cdiv(rows * (C / 4), 256) <= TW_MAX_BLOCKS && nrv_cdiv((long long)B * 50 * C, 256) <= TW_MAX_BLOCKS;
+    return rows * C <= (1ll << 40) && nrv_cdiv(rows * (C / 4), 256) <= NRV_MAX_BLOCKS && nrv_cdiv((long long)B * 50 * C, 256) <= NRV_MAX_BLOCKS;
 }
 
 template <bool FLIP>
 void peg_conv_launch(const float* src, const float* w, const float* bias, float* dst, int B, int H, int W, int C, int ks, hipStream_t st) {
     const long long items = (long long)B * H * W * (C / 4);
     const dim3 grid((unsigned)nrv_cdiv(items, 256));
-    if (ks == 3) hipLaunchKernelGGL((peg_conv_kernel<3, FLIP>), grid, dim3(256), 0, st, src, w, bias, dst, items, H, W, C);
-    else if (ks == 5) hipLaunchKernelGGL((peg_conv_kernel<5, FLIP>), grid, dim3(256), 0, st, src, w, bias, dst, items, H, W, C);
-    else hipLaunchKernelGGL((peg_conv_kernel<7, FLIP>), grid, dim3(256), 0, st, src, w, bias, dst, items, H, W, C);
+    NRV_DISPATCH_KS(ks, hipLaunchKernelGGL((peg_conv_kernel<KS, FLIP>), grid, dim3(256), 0, st, src, w, bias, dst, items, H, W, C));
 }
 
 }  // namespace
@@ -558,7 +542,8 @@ extern "C" int nrv_peg_bwd(const float* x_f32, const float* w, const float* dy_f
     const long long parts = (long long)B * (KK + 1) * C;
     hipLaunchKernelGGL(peg_dw_kernel, dim3((unsigned)nrv_cdiv(parts, 256)), dim3(256), 0, st, x_f32, dy_f32, part, parts, H, W, C, ks);
     NRV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(peg_wred_kernel, dim3((unsigned)nrv_cdiv((long long)(KK + 1) * C, 256)), dim3(256), 0, st, part, dw, dbias, B, C, KK);
+    // dw [C, KK] and dbias [C] = the per-sample partials summed over the samples in index order
+    hipLaunchKernelGGL(tap_wred_kernel<256>, dim3((unsigned)nrv_cdiv((long long)(KK + 1) * C, 256)), dim3(256), 0, st, part, dw, dbias, B, C, KK);
     NRV_CHECK_LAUNCH();
     return 0;
 }

@@ -2,14 +2,11 @@
 
 The generator (tests/golden/gen_golden_adapter.py) loads these into the reference's modules and stores only what the
 reference computes from them (outputs, loss, gradients) plus the module tree; the tests load the same tensors into the HIP
-modules.  Every tensor comes from a CPU torch.Generator seeded from the case seed and the tensor's name, so it does not
-depend on module construction order.  Stored outputs are float16 relative to their max-abs (`pack` / `unpack`): 2^-11
-relative per element, far below the 6e-3 / 1e-2 parity checks, at a quarter of the fp32 bytes.
+modules.  The per-name generator and the float16 packing are port_fixture's, re-exported here for the generator script.
 """
-import zlib
-
-import numpy as np
 import torch
+
+from port_fixture import _gen, pack, unpack  # noqa: F401
 
 # Adapter case: lucid ViT(image_size=64, patch_size=16, dim=128, depth=2, heads=2, dim_head=64, mlp_dim=256) + Adapter(M=3, 5 classes)
 ADAPTER_VIT = dict(image_size=64, patch_size=16, num_classes=10, dim=128, depth=2, heads=2, dim_head=64, mlp_dim=256)
@@ -17,10 +14,6 @@ ADAPTER_M, ADAPTER_CLASSES, ADAPTER_BATCH = 3, 5, 4
 # masks-and-memories case: bare Transformer(dim, depth, heads, dim_head, mlp_dim), per-sample memories, one fully masked row
 TR_ARGS = (64, 2, 2, 32, 128)
 TR_B, TR_NQ, TR_M, TR_FULL_ROW = 3, 21, 5, 4
-
-
-def _gen(seed: int, name: str) -> torch.Generator:
-    return torch.Generator().manual_seed(seed * 1_000_003 + zlib.crc32(name.encode()))
 
 
 def weights(state_dict, seed: int) -> dict:
@@ -59,14 +52,3 @@ def transformer_inputs(seed: int = 11):
     mask[TR_FULL_ROW] = False                      # one fully masked query row: uniform weights
     dy = torch.randn(TR_B, TR_NQ, dim, generator=g)
     return x, mems, mask, dy
-
-
-def pack(out: dict, key: str, t) -> None:
-    a = np.asarray(t.detach().float().numpy() if torch.is_tensor(t) else t, dtype=np.float32)
-    s = float(np.abs(a).max()) or 1.0
-    out[key] = (a / s).astype(np.float16)
-    out[key + ".scale"] = np.float32(s)
-
-
-def unpack(fx, key: str) -> torch.Tensor:
-    return torch.from_numpy(fx[key].astype(np.float32) * fx[key + ".scale"])

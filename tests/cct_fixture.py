@@ -2,13 +2,14 @@
 
 tests/golden/gen_golden_cct.py loads these into the reference's cct.py modules and stores what the reference computes (logits,
 CE loss, the gradient of every parameter), the module trees, a seeded-init record and the keep masks the reference drew in the
-dropout case; the tests load the same tensors into the HIP modules and into tests/cct_ref.py.  Seeds, packing and gradient
-sampling are swin_fixture's.
+dropout case; the tests load the same tensors into the HIP modules and into tests/cct_ref.py.  Seeds, the weight recipe,
+packing and gradient sampling are port_fixture's.
 """
 import numpy as np
 import torch
 
-from swin_fixture import _gen, grad_index, grad_sample, pack, pack_grads, pack_tree, unpack, unpack_grads, unpack_tree  # noqa: F401
+from port_fixture import (_gen, grad_index, grad_sample, image_inputs, pack, pack_grads, pack_tree, seeded_weights,  # noqa: F401
+                          unpack, unpack_grads, unpack_tree)
 
 BASE = dict(img_size=16, embedding_dim=64, n_input_channels=3, n_conv_layers=1, kernel_size=3, stride=1, padding=1, num_layers=2,
             num_heads=2, mlp_ratio=2, num_classes=10, stochastic_depth_rate=0.0)
@@ -64,35 +65,24 @@ def classifier_of(model):
 def weights(model, seed: int) -> dict:
     """Linear / Conv2d weights ~ N(0, 1/fan_in); LayerNorm weights 1 + 0.1 N(0, 1); class_emb 0.5 N(0, 1); a learnable
     positional_emb 0.2 N(0, 1), the frozen sine table as constructed; biases 0.02 N(0, 1)."""
-    out = {}
     params = dict(model.named_parameters())
-    for name, t in model.state_dict().items():
-        z = torch.randn(tuple(t.shape), generator=_gen(seed, name))
-        leaf = name.rsplit(".", 1)[-1]
+
+    def special(name, leaf, t, z):
         if leaf == "class_emb":
-            z = 0.5 * z
-        elif leaf == "positional_emb":
-            z = 0.2 * z if params[name].requires_grad else t.detach().clone()
-        elif t.dim() >= 2:
-            z = z / t[0].numel() ** 0.5
-        elif leaf == "weight":
-            z = 1.0 + 0.1 * z
-        else:
-            z = 0.02 * z
-        out[name] = z
-    return out
+            return 0.5 * z
+        if leaf == "positional_emb":
+            return 0.2 * z if params[name].requires_grad else t.detach().clone()
+    return seeded_weights(model.state_dict(), seed, special)
 
 
 def inputs(case: str):
     cfg, _, _, B, _ = CASES[case]
-    g = _gen(17, "inputs." + case)
-    if case == "cls":
+    if case == "cls":                                                       # tokens, not an image
+        g = _gen(17, "inputs." + case)
         x = torch.randn(B, cfg["sequence_length"], cfg["embedding_dim"], generator=g)
-    else:
-        h, w = cfg["img_size"] if isinstance(cfg["img_size"], tuple) else (cfg["img_size"],) * 2
-        x = torch.randn(B, cfg["n_input_channels"], h, w, generator=g)
-    y = torch.randint(0, cfg["num_classes"], (B,), generator=g)
-    return x, y
+        return x, torch.randint(0, cfg["num_classes"], (B,), generator=g)
+    h, w = cfg["img_size"] if isinstance(cfg["img_size"], tuple) else (cfg["img_size"],) * 2
+    return image_inputs(case, B, cfg["n_input_channels"], h, w, cfg["num_classes"])
 
 
 # ---- the keep masks of the dropout case -----------------------------------------------------------

@@ -2,16 +2,15 @@
 
 tests/golden/gen_golden_deepvit.py loads these into the reference's deepvit.py modules and stores what the reference computes
 (logits, CE loss, the gradient of every parameter) plus the module trees; the tests load the same tensors into the HIP modules
-and into tests/deepvit_ref.py.  Seeds, packing and gradient sampling are swin_fixture's.
+and into tests/deepvit_ref.py.  Seeds, the weight recipe, packing and gradient sampling are port_fixture's.
 
 Every case has at least 3 heads: with two, the LayerNorm over the heads leaves one degree of freedom per position and the
 gradient of reattn_weights is mostly cancellation (bf16 operand rounding alone moves it by 0.1 to 3 rel-L2), so a two-head model
 is no parity case.  The reference's DeepViT is softmax only: robust models have no recording and are checked against the
 restatement, whose Sinkhorn is pinned to the reference by sinkhorn_unit.npz.
 """
-import torch
-
-from swin_fixture import _gen, grad_index, grad_sample, pack, pack_grads, pack_tree, unpack, unpack_grads, unpack_tree  # noqa: F401
+from port_fixture import (_gen, grad_index, grad_sample, image_inputs, pack, pack_grads, pack_tree, seeded_weights,  # noqa: F401
+                          unpack, unpack_grads, unpack_tree, vit_tokens)
 
 SMALL = dict(image_size=64, patch_size=16, num_classes=10, dim=64, depth=2, heads=4, mlp_dim=128, dim_head=16)
 SMALL_NPARAMS = 117754
@@ -38,29 +37,11 @@ def build(module, case: str, **kw):
 def weights(model, seed: int) -> dict:
     """Linear weights ~ N(0, 1/fan_in); reattn_weights N(0, 1) (the reference's init); LayerNorm weights 1 + 0.1 N(0, 1);
     cls_token 0.5 N(0, 1); pos_embedding 0.2 N(0, 1); biases 0.02 N(0, 1)."""
-    out = {}
-    for name, t in model.state_dict().items():
-        z = torch.randn(tuple(t.shape), generator=_gen(seed, name))
-        leaf = name.rsplit(".", 1)[-1]
-        if leaf == "reattn_weights":
-            pass
-        elif name == "cls_token":
-            z = 0.5 * z
-        elif name == "pos_embedding":
-            z = 0.2 * z
-        elif t.dim() >= 2:
-            z = z / t[0].numel() ** 0.5
-        elif leaf == "weight":
-            z = 1.0 + 0.1 * z
-        else:
-            z = 0.02 * z
-        out[name] = z
-    return out
+    def special(name, leaf, t, z):
+        return z if leaf == "reattn_weights" else vit_tokens(name, leaf, t, z)
+    return seeded_weights(model.state_dict(), seed, special)
 
 
 def inputs(case: str):
     cfg, _, B = CASES[case]
-    g = _gen(17, "inputs." + case)
-    img = torch.randn(B, 3, cfg["image_size"], cfg["image_size"], generator=g)
-    y = torch.randint(0, cfg["num_classes"], (B,), generator=g)
-    return img, y
+    return image_inputs(case, B, 3, cfg["image_size"], cfg["image_size"], cfg["num_classes"])

@@ -3,12 +3,13 @@
 tests/golden/gen_golden_levit.py loads these into the reference's levit.py modules and stores what the reference computes
 (logits, CE loss, the gradient of every parameter, the running statistics after the forward) plus the module trees; the tests
 load the same tensors into the HIP modules and into tests/levit_ref.py.  Seeds, packing and gradient sampling are
-swin_fixture's.
+port_fixture's; the weight recipe (batch norms, bias tables, running statistics) is its own.
 """
 import torch
 from torch import nn
 
-from swin_fixture import _gen, grad_index, grad_sample, pack, pack_grads, pack_tree, unpack, unpack_grads, unpack_tree  # noqa: F401
+from port_fixture import (_gen, grad_index, grad_sample, image_inputs, pack, pack_grads, pack_tree, unpack, unpack_grads,  # noqa: F401
+                          unpack_tree)
 
 BUILDERS = ("LeViT_128S", "LeViT_128", "LeViT_192", "LeViT_256", "LeViT_384")
 NPARAMS = {"LeViT_128S": 7391290, "LeViT_128": 8828168, "LeViT_192": 10561301, "LeViT_256": 18379852, "LeViT_384": 38358300}
@@ -78,10 +79,7 @@ def weights(model, seed: int) -> dict:
 
 def inputs(case: str):
     cfg, _, _, B = CASES[case]
-    g = _gen(17, "inputs." + case)
-    img = torch.randn(B, 3, cfg["img_size"], cfg["img_size"], generator=g)
-    y = torch.randint(0, cfg["num_classes"], (B,), generator=g)
-    return img, y
+    return image_inputs(case, B, 3, cfg["img_size"], cfg["img_size"], cfg["num_classes"])
 
 
 def running_stats(model):

@@ -2,11 +2,12 @@
 
 tests/golden/gen_golden_patchconvnet.py loads these into the reference's patch_convnet.py modules and stores what the reference
 computes (logits, CE loss, the gradient of every parameter) plus the module trees; the tests load the same tensors into the HIP
-modules and into tests/patchconvnet_ref.py.  Seeds, packing and gradient sampling are swin_fixture's.
+modules and into tests/patchconvnet_ref.py.  Seeds, the weight recipe, packing and gradient sampling are port_fixture's.
 """
 import torch
 
-from swin_fixture import _gen, grad_index, grad_sample, pack, pack_grads, pack_tree, unpack, unpack_grads, unpack_tree  # noqa: F401
+from port_fixture import (_gen, grad_index, grad_sample, image_inputs, pack, pack_grads, pack_tree, seeded_weights,  # noqa: F401
+                          unpack, unpack_grads, unpack_tree, vit_tokens)
 
 BUILDERS = ("S60", "S120", "B60", "B120", "L60", "L120")
 # under torch.manual_seed(0) with 100 classes (the reference's CIFAR-100 script)
@@ -34,27 +35,11 @@ def build(module, case: str):
 def weights(model, seed: int) -> dict:
     """Rank >= 2 weights ~ N(0, 1/fan_in); LayerNorm weights 1 + 0.1 N(0, 1); gamma_* 0.1 (1 + 0.1 N(0, 1)) (the reference's 1e-4
     would hide every branch in the logits); cls_token 0.5 N(0, 1); biases 0.02 N(0, 1)."""
-    out = {}
-    for name, t in model.state_dict().items():
-        z = torch.randn(tuple(t.shape), generator=_gen(seed, name))
-        leaf = name.rsplit(".", 1)[-1]
-        if leaf.startswith("gamma_"):
-            z = 0.1 * (1.0 + 0.1 * z)
-        elif name == "cls_token":
-            z = 0.5 * z
-        elif t.dim() >= 2:
-            z = z / t[0].numel() ** 0.5
-        elif leaf == "weight":
-            z = 1.0 + 0.1 * z
-        else:
-            z = 0.02 * z
-        out[name] = z
-    return out
+    def special(name, leaf, t, z):
+        return 0.1 * (1.0 + 0.1 * z) if leaf.startswith("gamma_") else vit_tokens(name, leaf, t, z)
+    return seeded_weights(model.state_dict(), seed, special)
 
 
 def inputs(case: str):
     cfg, _, B = CASES[case]
-    g = _gen(17, "inputs." + case)
-    img = torch.randn(B, 3, cfg["img_size"], cfg["img_size"], generator=g)
-    y = torch.randint(0, cfg["num_classes"], (B,), generator=g)
-    return img, y
+    return image_inputs(case, B, 3, cfg["img_size"], cfg["img_size"], cfg["num_classes"])

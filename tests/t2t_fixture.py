@@ -2,11 +2,10 @@
 
 tests/golden/gen_golden_t2t.py loads these into the reference's t2t.py modules and stores what the reference computes (logits,
 CE loss, the gradient of every parameter) plus the module trees; the tests load the same tensors into the HIP modules and into
-tests/t2t_ref.py.  Seeds, packing and gradient sampling are swin_fixture's.
+tests/t2t_ref.py.  Seeds, the weight recipe, packing and gradient sampling are port_fixture's.
 """
-import torch
-
-from swin_fixture import _gen, grad_index, grad_sample, pack, pack_grads, pack_tree, unpack, unpack_grads, unpack_tree  # noqa: F401
+from port_fixture import (_gen, grad_index, grad_sample, image_inputs, pack, pack_grads, pack_tree, seeded_weights,  # noqa: F401
+                          unpack, unpack_grads, unpack_tree, vit_tokens)
 
 SMALL = dict(image_size=64, num_classes=10, dim=64, depth=2, heads=2, mlp_dim=128, dim_head=32)
 # name -> (model config, robust, train, batch)
@@ -40,27 +39,9 @@ def build(module, case: str, sinkhorn=None):
 def weights(model, seed: int) -> dict:
     """Linear weights ~ N(0, 1/fan_in); LayerNorm weights 1 + 0.1 N(0, 1); cls_token 0.5 N(0, 1); pos_embedding 0.2 N(0, 1);
     biases 0.02 N(0, 1)."""
-    out = {}
-    for name, t in model.state_dict().items():
-        z = torch.randn(tuple(t.shape), generator=_gen(seed, name))
-        leaf = name.rsplit(".", 1)[-1]
-        if name == "cls_token":
-            z = 0.5 * z
-        elif name == "pos_embedding":
-            z = 0.2 * z
-        elif t.dim() >= 2:
-            z = z / t[0].numel() ** 0.5
-        elif leaf == "weight":
-            z = 1.0 + 0.1 * z
-        else:
-            z = 0.02 * z
-        out[name] = z
-    return out
+    return seeded_weights(model.state_dict(), seed, vit_tokens)
 
 
 def inputs(case: str):
     cfg, _, _, B = CASES[case]
-    g = _gen(17, "inputs." + case)
-    img = torch.randn(B, cfg.get("channels", 3), cfg["image_size"], cfg["image_size"], generator=g)
-    y = torch.randint(0, cfg["num_classes"], (B,), generator=g)
-    return img, y
+    return image_inputs(case, B, cfg.get("channels", 3), cfg["image_size"], cfg["image_size"], cfg["num_classes"])

@@ -2,23 +2,20 @@
 tests/cait_ref.py: logits, loss and every parameter's gradient, softmax and robust; 224-px models with 4 and 16 heads; layer
 dropout on seeded draws; eval mode; Trainer.step and Trainer.capture; reruns.
 
-Bounds follow test_levit_gpu.py / test_patchconvnet_gpu.py: the HIP result's rel-L2 to the fp32 restatement may be at most twice
-the bf16-operand emulation's own error plus 1e-2, per logits tensor and per parameter gradient.  With robust=True the class
+The bound is port_checks.judge's, with both restatements (fp32, bf16-rounded operands) on the CPU.  With robust=True the class
 stage has one query, the Sinkhorn weights are uniform and the gradients of its to_q and mix_heads_pre_attn vanish: those are
-checked to be numerically zero (abs max < 1e-4) instead, and nothing else is left out."""
+checked to be numerically zero (abs max < 1e-4) on both sides instead, and nothing else is left out."""
 import os
 import random
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import cait_fixture as CF  # noqa: E402
-import cait_ref as R  # noqa: E402
-
-from noise_robust_vit_amd import cait as C  # noqa: E402
+import cait_fixture as CF
+import cait_ref as R
+import port_checks as PC
+from noise_robust_vit_amd import cait as C
 
 pytestmark = pytest.mark.gpu
 FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cait_small.npz")
@@ -35,59 +32,16 @@ def fx():
     return np.load(FIX)
 
 
-def _rel(a, b):
-    a, b = a.detach().float().cpu().reshape(-1), b.detach().float().cpu().reshape(-1)
-    return float((a - b).norm() / (b.norm() + 1e-30))
-
-
-def _hip(model, x, y):
-    model.zero_grad(set_to_none=True)
-    logits = model(x)
-    loss = torch.nn.functional.cross_entropy(logits, y)
-    if model.training:
-        loss.backward()
-    return logits.detach(), loss.detach(), {k: p.grad for k, p in model.named_parameters()}
-
-
-def _vanishes(model, k):
+def _compare(model, x, y, kept=None, **rules):
+    """kept: the layers a layer-dropout draw keeps, (patch stage, class stage); the others must take no part in the step"""
     robust = model.cls_transformer.layers[0][0].fn.fn.robust
-    return robust and k.startswith("cls_transformer") and k.endswith(("to_q.weight", "mix_heads_pre_attn"))
-
-
-def _compare(model, x, y, kept=None, fixture=None, hip=None):
-    """HIP vs the fp32 restatement (and the reference fixture when given), bounded by the bf16-operand emulation's error."""
-    logits, loss, grads = hip if hip is not None else _hip(model, x, y)
-    cpu = model.to("cpu")
-    l32, s32, g32 = R.cait_loss_and_grads(cpu, x.cpu(), y.cpu(), kept=kept)
-    l16, _, g16 = R.cait_loss_and_grads(cpu, x.cpu(), y.cpu(), kept=kept, bf16_operands=True)
-    model.to(x.device)
-    bound = 2 * _rel(l16, l32) + 1e-2
-    print(f"logits rel {_rel(logits, l32):.3e} bound {bound:.3e}")
-    assert _rel(logits, l32) <= bound, (_rel(logits, l32), bound)
-    assert abs(loss.item() - s32.item()) <= 2e-2 * max(1.0, abs(s32.item()))
-    if fixture is not None:
-        fx, case = fixture
-        assert _rel(logits, CF.unpack(fx, case + ".logits")) <= bound
-    if model.training:
-        ref = CF.unpack_grads(fixture[0], fixture[1]) if fixture is not None else None
-        dropped = set()
-        if kept is not None:
-            for pre, t, ks in (("patch_transformer", model.patch_transformer, kept[0]), ("cls_transformer", model.cls_transformer, kept[1])):
-                dropped |= {f"{pre}.layers.{i}." for i in range(len(t.layers)) if i not in ks}
-        for k, g in grads.items():
-            if any(k.startswith(d) for d in dropped):
-                assert g is None or float(g.abs().max()) == 0.0, k          # a dropped layer takes no part in the step
-                continue
-            assert g is not None, k
-            if _vanishes(model, k):
-                assert float(g.abs().max()) < 1e-4 and float(g32[k].abs().max()) < 1e-4, k
-                continue
-            b = 2 * _rel(g16[k], g32[k]) + 1e-2
-            print(f"{k}: rel {_rel(g, g32[k]):.3e} bound {b:.3e}")
-            assert _rel(g, g32[k]) <= b, (k, _rel(g, g32[k]), b)
-            if ref is not None:
-                assert _rel(CF.grad_sample(k, g.cpu()), ref[k]) <= b + 1e-3, k
-    return logits, grads
+    dropped = set()
+    if kept is not None:
+        for pre, t, ks in (("patch_transformer", model.patch_transformer, kept[0]), ("cls_transformer", model.cls_transformer, kept[1])):
+            dropped |= {f"{pre}.layers.{i}." for i in range(len(t.layers)) if i not in ks}
+    return PC.compare(model, x, y, lambda m, x, y, low: R.cait_loss_and_grads(m, x, y, kept=kept, bf16_operands=low), on_cpu=True,
+                      vanishes=lambda k, r: robust and k.startswith("cls_transformer") and k.endswith(("to_q.weight", "mix_heads_pre_attn")),
+                      skip=PC.dropped_layers(dropped), **rules)
 
 
 @pytest.mark.parametrize("case", list(CF.CASES))
@@ -96,7 +50,8 @@ def test_fixture_parity(dev, fx, case):
     m.load_state_dict(CF.weights(m, 3))
     m = m.to(dev)
     img, y = CF.inputs(case)
-    _compare(m, img.to(dev), y.to(dev), fixture=(fx, case))
+    _compare(m, img.to(dev), y.to(dev), fixture_logits=CF.unpack(fx, case + ".logits"),
+             fixture_grads=CF.unpack_grads(fx, case) if m.training else None)
 
 
 def _model(dev, cfg, **kw):
@@ -133,31 +88,26 @@ def test_layer_dropout_on_seeded_draws(dev, robust):
     cfg = dict(CF.SMALL, depth=4, cls_depth=2, layer_dropout=0.5, robust=robust)
     m = _model(dev, cfg).train()
     x, y = _batch(dev, 3, 64)
-    torch.manual_seed(11); random.seed(11)
+
+    def seed(_=None):
+        torch.manual_seed(11); random.seed(11)
+    seed()
     kept = ([int(i) for i in C.dropout_layers(list(range(4)), 0.5)], [int(i) for i in C.dropout_layers(list(range(2)), 0.5)])
     assert len(kept[0]) < 4 or len(kept[1]) < 2, kept                       # the seed does drop something
-    torch.manual_seed(11); random.seed(11)
-    hip = _hip(m, x, y)
-    _compare(m, x, y, kept=kept, hip=hip)
+    _compare(m, x, y, kept=kept, pre=seed)
     # the draw is made in eval mode too (cait.py:153), from the same generator
     m.eval()
-    torch.manual_seed(11); random.seed(11)
+    seed()
     with torch.no_grad():
         a = m(x)
     l32, _, _ = R.cait_loss_and_grads(m.to("cpu"), x.cpu(), y.cpu(), kept=kept)
     m.to(dev)
-    assert _rel(a, l32) <= 3e-2
+    assert PC.rel(a, l32) <= 3e-2
 
 
 @pytest.mark.parametrize("robust", [False, True])
 def test_reruns_are_bit_identical(dev, robust):
-    m = _model(dev, dict(M224, robust=robust)).train()
-    x, y = _batch(dev, 2)
-    runs = []
-    for _ in range(2):
-        lg, _, g = _hip(m, x, y)
-        runs.append([lg] + [t.clone() for t in g.values()])
-    assert all(torch.equal(a, b) for a, b in zip(*runs))
+    PC.check_reruns_bit_identical(_model(dev, dict(M224, robust=robust)).train(), *_batch(dev, 2))
 
 
 def test_transformer_with_and_without_context(dev):
@@ -174,33 +124,21 @@ def test_transformer_with_and_without_context(dev):
         x32 = x.detach().cpu().requires_grad_(True)
         c32 = ctx_.detach().cpu().requires_grad_(True) if ctx_ is not None else None
         ref = R._layer(P, "layers.0.", x32, c32, a.heads, a.scale, True, (1e-5, 1e-5))
-        assert _rel(out, ref) <= 2e-2
+        assert PC.rel(out, ref) <= 2e-2
         w = torch.randn(ref.shape, generator=g)
         x.grad = None; c.grad = None
         (out * w.to(dev)).sum().backward()
         (ref * w).sum().backward()
-        assert _rel(x.grad, x32.grad) <= 3e-2
+        assert PC.rel(x.grad, x32.grad) <= 3e-2
         if ctx_ is not None:
-            assert _rel(c.grad, c32.grad) <= 3e-2
+            assert PC.rel(c.grad, c32.grad) <= 3e-2
 
 
 def test_trainer_step_and_capture(dev):
+    PC.check_eager_vs_captured(lambda: _model(dev, M224).train(), *_batch(dev, 8, seed=11), steps=2)
     from noise_robust_vit_amd.train import TrainConfig, Trainer
-    a = _model(dev, M224).train()
-    b = _model(dev, M224).train()
-    cfg = TrainConfig(lr=1e-3)
-    ta, tb = Trainer(a, cfg), Trainer(b, cfg)
-    x, y = _batch(dev, 8, seed=11)
-    ta.capture(x, y)
-    la = [ta.step(x, y) for _ in range(2)]
-    lb = [tb.step(x, y) for _ in range(2)]
-    assert all(torch.equal(u, v) for u, v in zip(la, lb)), (la, lb)
-    for (n, p), q in zip(a.named_parameters(), b.parameters()):
-        assert torch.equal(p, q), n
-    losses = [lb[-1].item()] + [tb.step(x, y).item() for _ in range(20)]
-    assert losses[-1] < losses[0], losses
     with pytest.raises(RuntimeError, match="layer_dropout"):
-        Trainer(_model(dev, CF.SMALL, layer_dropout=0.2).train(), cfg).capture(*_batch(dev, 2, 64))
+        Trainer(_model(dev, CF.SMALL, layer_dropout=0.2).train(), TrainConfig(lr=1e-3)).capture(*_batch(dev, 2, 64))
 
 
 def test_trainer_robust_loss_falls(dev):

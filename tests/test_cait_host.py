@@ -1,22 +1,18 @@
 """CPU: the CaiT module tree, seeded init, strict state_dict loading, layer-dropout draws and refusals, the fp32 restatement
 against the reference fixture, and the talking-heads prototypes in the header, the binding and the library's exports (no GPU)."""
 import os
-import re
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import cait_fixture as CF  # noqa: E402
-import cait_ref as R  # noqa: E402
+import cait_fixture as CF
+import cait_ref as R
+import port_checks as PC
+from noise_robust_vit_amd import cait as C
+from noise_robust_vit_amd._lib import NrvError
 
-from noise_robust_vit_amd import cait as C  # noqa: E402
-from noise_robust_vit_amd._lib import NrvError  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIX = os.path.join(ROOT, "tests", "golden", "cait_small.npz")
+FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cait_small.npz")
 NEW = ("nrv_th_softmax_fwd", "nrv_th_softmax_bwd_workspace", "nrv_th_softmax_bwd", "nrv_head_mix_fwd", "nrv_head_mix_bwd_workspace",
        "nrv_head_mix_bwd")
 
@@ -36,42 +32,18 @@ def test_package_exports_cait():
 @pytest.mark.parametrize("case", list(CF.CASES))
 def test_restatement_matches_reference_fixture(fx, case):
     m = CF.build(C, case)
-    w = CF.weights(m, 3)
-    m.load_state_dict(w, strict=True)
-    tree = CF.unpack_tree(fx, case)
-    assert list(tree) == list(m.state_dict())
-    for k, (shape, s) in tree.items():
-        assert tuple(m.state_dict()[k].shape) == shape, k
-        assert abs(float(w[k].double().sum()) - s) <= 1e-9 * max(1.0, abs(s)), k
-    img, y = CF.inputs(case)
-    logits, loss, grads = R.cait_loss_and_grads(m, img, y)
-    ref = CF.unpack(fx, case + ".logits")
-    assert float((logits - ref).abs().max()) <= 2e-3 * float(ref.abs().max())
-    assert abs(loss.item() - float(fx[case + ".loss"])) < 1e-4
-    if m.training:
-        G = CF.unpack_grads(fx, case)
-        assert sorted(G) == sorted(grads)
-        for k, g in G.items():
-            a = CF.grad_sample(k, grads[k])
-            if CF.CASES[case][1] and k.startswith("cls_transformer") and k.endswith(("to_q.weight", "mix_heads_pre_attn")):
-                # one query under Sinkhorn: uniform weights, the gradient is rounding noise on both sides
-                assert float(a.abs().max()) < 1e-6 and float(g.abs().max()) < 1e-6, k
-                continue
-            assert float((a - g).norm() / (g.norm() + 1e-12)) < 2e-3, k
+    PC.check_keys_and_sums(m, CF.weights(m, 3), fx, case, rtol=1e-9)
+
+    def noise(k, g):
+        # one query under Sinkhorn: uniform weights, the gradient is rounding noise on both sides
+        return CF.CASES[case][1] and k.startswith("cls_transformer") and k.endswith(("to_q.weight", "mix_heads_pre_attn"))
+    PC.check_restatement(R.cait_loss_and_grads(m, *CF.inputs(case)), fx, case, m.training, loss_tol=1e-4, grad_tol=2e-3, noise=noise)
 
 
 @pytest.mark.parametrize("name,cfg", [("small", CF.SMALL), ("full", CF.FULL)])
 def test_seeded_init_matches_reference(fx, name, cfg):
     torch.manual_seed(0)
-    m = C.CaiT(**cfg)
-    sd = m.state_dict()
-    tree = CF.unpack_tree(fx, name)
-    assert list(tree) == list(sd)
-    for k, (shape, s) in tree.items():
-        assert tuple(sd[k].shape) == shape, k
-        v = float(sd[k].double().sum())
-        assert abs(v - s) <= 1e-6 * max(1.0, abs(s)), (k, v, s)
-    assert sum(p.numel() for p in m.parameters()) == int(fx[name + ".nparams"])
+    PC.check_seeded_init(C.CaiT(**cfg), fx, name, rtol=1e-6, atol=0.0)
     if name == "small":
         assert int(fx[name + ".nparams"]) == CF.SMALL_NPARAMS
 
@@ -180,18 +152,7 @@ def test_capture_refuses_layer_dropout():
 
 
 def test_talking_heads_prototypes_in_header_binding_and_exports():
-    from noise_robust_vit_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "nrv.h")).read()
-    assert int(re.search(r"#define NRV_ABI_VERSION (\d+)\b", hdr).group(1)) == _lib.ABI_VERSION
-    for name in NEW:
-        assert re.search(r"\b" + name + r"\s*\(", hdr), name
-        assert name in _lib.SIGNATURES, name
-    from noise_robust_vit_amd import build
-    import ctypes
-    lib = ctypes.CDLL(build.build())
-    for name in NEW:
-        assert hasattr(lib, name), name
-    assert lib.nrv_abi_version() == _lib.ABI_VERSION
+    lib = PC.check_prototypes(NEW)
     # shapes are classified on the host, before any launch: callable without a GPU
     assert lib.nrv_th_softmax_fwd(16, 16, 16, 16, 16, 0, 1, 17, 4, 4, None) == -2
     assert lib.nrv_head_mix_fwd(16, 16, 16, 0, 1, 4, 1, 1026, None) == -2

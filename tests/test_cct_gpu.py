@@ -3,23 +3,19 @@ tests/cct_ref.py: logits, loss and every parameter's gradient for each fixture c
 recorded masks on both sides); eval mode; reruns; the kernels a training step launches; Trainer.step and Trainer.capture; a
 reference-shaped state_dict round trip.
 
-Bounds follow test_pit_gpu.py: the HIP result's rel-L2 to the fp32 restatement may be at most twice the rel-L2 of the same
-restatement under bf16 autocast plus 1e-2, per logits tensor and per parameter gradient; both restatements run on the same GPU
-in the same test.  A gradient that vanishes in the restatement (abs max < 1e-4; attention_pool.bias, zero in exact arithmetic)
-is checked to vanish in the HIP result; the frozen sine table has no gradient on either side; nothing else is left out."""
+The bound is port_checks.judge's, with both restatements (fp32, bf16 autocast) on the same GPU in the same test.  A gradient
+that vanishes in the restatement (abs max < 1e-4; attention_pool.bias, zero in exact arithmetic) is checked to vanish in the
+HIP result; the frozen sine table has no gradient on either side; nothing else is left out."""
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import cct_fixture as CF  # noqa: E402
-import cct_ref as R  # noqa: E402
-
-from noise_robust_vit_amd import cct as V  # noqa: E402
-from noise_robust_vit_amd import kernels as K  # noqa: E402
+import cct_fixture as CF
+import cct_ref as R
+import port_checks as PC
+from noise_robust_vit_amd import cct as V
 
 pytestmark = pytest.mark.gpu
 FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cct_small.npz")
@@ -36,47 +32,12 @@ def fx():
     return np.load(FIX)
 
 
-def _rel(a, b):
-    a, b = a.detach().float().cpu().reshape(-1), b.detach().float().cpu().reshape(-1)
-    return float((a - b).norm() / (b.norm() + 1e-30))
-
-
-def _hip(model, x, y, masks=None):
-    model.zero_grad(set_to_none=True)
-    if masks is not None:
-        CF.inject_masks(model, masks)                                      # the drop-path iterator serves one forward
-    logits = model(x)
-    loss = torch.nn.functional.cross_entropy(logits, y)
-    if model.training:
-        loss.backward()
-    return logits.detach(), loss.detach(), {k: p.grad for k, p in model.named_parameters()}
-
-
-def _compare(model, x, y, fixture=None, masks=None):
-    logits, loss, grads = _hip(model, x, y, masks)
-    l32, s32, g32 = R.cct_loss_and_grads(model, x, y, masks=masks)
-    l16, _, g16 = R.cct_loss_and_grads(model, x, y, autocast=True, masks=masks)
-    bound = 2 * _rel(l16, l32) + 1e-2
-    print(f"logits rel {_rel(logits, l32):.3e} bound {bound:.3e}; loss {loss.item():.5f} vs {s32.item():.5f}")
-    assert _rel(logits, l32) <= bound, (_rel(logits, l32), bound)
-    assert abs(loss.item() - s32.item()) <= 2e-2 * max(1.0, abs(s32.item()))
-    if fixture is not None:
-        fxd, case = fixture
-        assert _rel(logits, CF.unpack(fxd, case + ".logits")) <= bound
-    if model.training:
-        assert set(grads) == set(g32)
-        for k, g in grads.items():
-            if g32[k] is None:
-                assert g is None and k.endswith("positional_emb"), k      # the frozen sine table: no gradient on either side
-                continue
-            assert g is not None, k
-            if float(g32[k].abs().max()) < 1e-4:
-                assert float(g.abs().max()) < 1e-4, k
-                continue
-            b = 2 * _rel(g16[k], g32[k]) + 1e-2
-            print(f"{k}: rel {_rel(g, g32[k]):.3e} bound {b:.3e}")
-            assert _rel(g, g32[k]) <= b, (k, _rel(g, g32[k]), b)
-    return logits, grads
+def _compare(model, x, y, masks=None, **rules):
+    """masks: the recorded keep masks, injected into the HIP model (the drop-path iterator serves one forward) and handed to
+    both restatements"""
+    return PC.compare(model, x, y, lambda m, x, y, low: R.cct_loss_and_grads(m, x, y, autocast=low, masks=masks),
+                      pre=(lambda m: CF.inject_masks(m, masks)) if masks is not None else None,
+                      skip=PC.frozen("positional_emb"), **rules)
 
 
 @pytest.mark.parametrize("case", list(CF.CASES))
@@ -86,7 +47,7 @@ def test_fixture_parity(dev, fx, case):
     m = m.to(dev)
     x, y = CF.inputs(case)
     masks = CF.unpack_masks(fx, case, len(CF.classifier_of(m).blocks)) if case == "drop" else None
-    _compare(m, x.to(dev), y.to(dev), fixture=(fx, case), masks=masks)
+    _compare(m, x.to(dev), y.to(dev), masks=masks, fixture_logits=CF.unpack(fx, case + ".logits"))
 
 
 def _model(dev, cfg, **kw):
@@ -113,23 +74,14 @@ def test_eval_mode_is_deterministic(dev):
 @pytest.mark.parametrize("robust", [False, True])
 def test_reruns_are_bit_identical(dev, robust):
     m = _model(dev, SMALL, robust=robust, attention_dropout=0.0, n_conv_layers=2).train()
-    x, y = _batch(dev, 2)
-    runs = []
-    for _ in range(2):
-        lg, _, g = _hip(m, x, y)
-        runs.append([lg] + [t.clone() for t in g.values() if t is not None])
-    assert all(torch.equal(a, b) for a, b in zip(*runs))
+    PC.check_reruns_bit_identical(m, *_batch(dev, 2))
 
 
 def test_a_step_launches_the_new_kernels(dev):
     """relu_maxpool_fwd / _bwd once per conv layer, seqpool once, layernorm_f32_fwd num_layers + 1 times, attn_fwd num_layers
     times, and no strided batched GEMM at attention_dropout=0"""
     m = _model(dev, SMALL, attention_dropout=0.0, n_conv_layers=2).train()
-    x, y = _batch(dev, 2)
-    _hip(m, x, y)
-    with K.LaunchProfile() as prof:
-        _hip(m, x, y)
-    names = prof.summary()
+    names = PC.profiled_step(m, *_batch(dev, 2))
     layers, convs = len(m.classifier.blocks), len(m.tokenizer.conv_layers)
     assert (layers, convs) == (2, 2)
     for n in ("conv_unfold", "conv_fold", "relu_maxpool_fwd", "relu_maxpool_bwd", "layernorm_f32_fwd", "layernorm_f32_bwd", "seqpool_fwd",
@@ -144,12 +96,10 @@ def test_a_step_launches_the_new_kernels(dev):
 
 
 def test_the_default_attention_dropout_takes_the_composed_path(dev):
+    from noise_robust_vit_amd import kernels as K
     m = _model(dev, SMALL).train()                                         # the reference's attention dropout 0.1
     x, y = _batch(dev, 2)
-    _hip(m, x, y)
-    with K.LaunchProfile() as prof:
-        _hip(m, x, y)
-    names = prof.summary()
+    names = PC.profiled_step(m, x, y)
     assert "bgemm" in names and "attn_fwd" not in names, sorted(names)
     with K.LaunchProfile() as prof:
         with torch.no_grad():
@@ -158,21 +108,10 @@ def test_the_default_attention_dropout_takes_the_composed_path(dev):
 
 
 def test_trainer_step_and_capture(dev):
-    from noise_robust_vit_amd.train import TrainConfig, Trainer
     kw = dict(attention_dropout=0.0, stochastic_depth_rate=0.0)
-    a = _model(dev, SMALL, **kw).train()
-    b = _model(dev, SMALL, **kw).train()
-    cfg = TrainConfig(lr=1e-3)
-    ta, tb = Trainer(a, cfg), Trainer(b, cfg)
     x, y = _batch(dev, 8, seed=11)
-    ta.capture(x, y)
-    la = [ta.step(x, y) for _ in range(3)]
-    lb = [tb.step(x, y) for _ in range(3)]
-    assert all(torch.equal(u, v) for u, v in zip(la, lb)), (la, lb)
-    for (n, p), q in zip(a.named_parameters(), b.parameters()):
-        assert torch.equal(p, q), n
-    ev = tb.eval_step(x, y)
-    assert torch.isfinite(ev).all()
+    tb = PC.check_eager_vs_captured(lambda: _model(dev, SMALL, **kw).train(), x, y, falls=0)
+    assert torch.isfinite(tb.eval_step(x, y)).all()
 
 
 @pytest.mark.parametrize("captured", [False, True])
@@ -199,16 +138,4 @@ def test_trainer_robust_loss_falls(dev):
 
 
 def test_state_dict_round_trip(dev):
-    """A reference-shaped state_dict (the fixture's keys and shapes) loads strictly, gives the same logits after a save / load
-    cycle into a fresh model, and the bf16 weight images follow the loaded values."""
-    a = _model(dev, SMALL).eval()
-    x, _ = _batch(dev, 2)
-    with torch.no_grad():
-        la = a(x)
-        sd = {k: v.detach().cpu().clone() for k, v in a.state_dict().items()}
-        torch.manual_seed(7)
-        b = V.CCT(**SMALL).to(dev).eval()
-        lb0 = b(x)
-        b.load_state_dict(sd, strict=True)
-        lb = b(x)
-    assert not torch.equal(la, lb0) and torch.equal(la, lb)
+    PC.check_state_dict_round_trip(_model(dev, SMALL).eval(), lambda: V.CCT(**SMALL), _batch(dev, 2)[0])

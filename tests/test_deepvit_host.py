@@ -2,22 +2,18 @@
 against the reference fixture, and the re-attention prototypes in the header, the binding and the library's exports (no GPU)."""
 import ctypes
 import os
-import re
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import deepvit_fixture as DF  # noqa: E402
-import deepvit_ref as R  # noqa: E402
+import deepvit_fixture as DF
+import deepvit_ref as R
+import port_checks as PC
+from noise_robust_vit_amd import deepvit as D
+from noise_robust_vit_amd._lib import NrvError
 
-from noise_robust_vit_amd import deepvit as D  # noqa: E402
-from noise_robust_vit_amd._lib import NrvError  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIX = os.path.join(ROOT, "tests", "golden", "deepvit_small.npz")
+FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "deepvit_small.npz")
 NEW = ("nrv_reattn_softmax_fwd", "nrv_reattn_softmax_bwd_workspace", "nrv_reattn_softmax_bwd", "nrv_reattn_norm_fwd",
        "nrv_reattn_norm_bwd_workspace", "nrv_reattn_norm_bwd")
 
@@ -42,38 +38,14 @@ def test_fixture_cases_have_at_least_three_heads():
 @pytest.mark.parametrize("case", list(DF.CASES))
 def test_restatement_matches_reference_fixture(fx, case):
     m = DF.build(D, case)
-    w = DF.weights(m, 3)
-    m.load_state_dict(w, strict=True)
-    tree = DF.unpack_tree(fx, case)
-    assert list(tree) == list(m.state_dict())
-    for k, (shape, s) in tree.items():
-        assert tuple(m.state_dict()[k].shape) == shape, k
-        assert abs(float(w[k].double().sum()) - s) <= 1e-9 * max(1.0, abs(s)), k
-    img, y = DF.inputs(case)
-    logits, loss, grads = R.deepvit_loss_and_grads(m, img, y)
-    ref = DF.unpack(fx, case + ".logits")
-    assert float((logits - ref).abs().max()) <= 2e-3 * float(ref.abs().max())
-    assert abs(loss.item() - float(fx[case + ".loss"])) < 1e-4
-    if m.training:
-        G = DF.unpack_grads(fx, case)
-        assert sorted(G) == sorted(grads)
-        for k, g in G.items():
-            a = DF.grad_sample(k, grads[k])
-            assert float((a - g).norm() / (g.norm() + 1e-12)) < 2e-3, k
+    PC.check_keys_and_sums(m, DF.weights(m, 3), fx, case, rtol=1e-9)
+    PC.check_restatement(R.deepvit_loss_and_grads(m, *DF.inputs(case)), fx, case, m.training, loss_tol=1e-4, grad_tol=2e-3)
 
 
 @pytest.mark.parametrize("name,cfg", [("small", DF.SMALL), ("full", DF.FULL)])
 def test_seeded_init_matches_reference(fx, name, cfg):
     torch.manual_seed(0)
-    m = D.DeepViT(**cfg)
-    sd = m.state_dict()
-    tree = DF.unpack_tree(fx, name)
-    assert list(tree) == list(sd)
-    for k, (shape, s) in tree.items():
-        assert tuple(sd[k].shape) == shape, k
-        v = float(sd[k].double().sum())
-        assert abs(v - s) <= 1e-6 * max(1.0, abs(s)), (k, v, s)
-    assert sum(p.numel() for p in m.parameters()) == int(fx[name + ".nparams"])
+    PC.check_seeded_init(D.DeepViT(**cfg), fx, name, rtol=1e-6, atol=0.0)
     if name == "small":
         assert int(fx[name + ".nparams"]) == DF.SMALL_NPARAMS
 
@@ -174,17 +146,7 @@ def test_recording_cpu_tensors_and_direct_calls_are_refused():
 
 def test_reattn_prototypes_in_header_binding_and_exports():
     from noise_robust_vit_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "nrv.h")).read()
-    assert int(re.search(r"#define NRV_ABI_VERSION (\d+)\b", hdr).group(1)) == _lib.ABI_VERSION == 19
-    for name in NEW:
-        assert re.search(r"\b" + name + r"\s*\(", hdr), name
-        assert name in _lib.SIGNATURES, name
-    from noise_robust_vit_amd import build
-    assert "nrv_reattn.hip" in build.SOURCES
-    raw = ctypes.CDLL(build.build())
-    for name in NEW:
-        assert hasattr(raw, name), name
-    assert raw.nrv_abi_version() == _lib.ABI_VERSION
+    PC.check_prototypes(NEW, abi=19, source="nrv_reattn.hip")
     # shapes are classified on the host, before any launch: callable without a GPU
     lib = _lib.load()
     eps, zero, big = ctypes.c_float(1e-5), ctypes.c_float(0.0), ctypes.c_size_t(1 << 30)

@@ -1,23 +1,18 @@
 """CPU: the PatchConvNet module tree, seeded init and refusals, the fp32 restatement against the reference fixture, and the
 ABI 17 prototypes in the header, the binding and the library's exports (no GPU)."""
 import os
-import re
-import sys
-from functools import partial
 
 import numpy as np
 import pytest
 import torch
 from torch import nn
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import patchconvnet_fixture as PF  # noqa: E402
-import patchconvnet_ref as R  # noqa: E402
+import patchconvnet_fixture as PF
+import patchconvnet_ref as R
+import port_checks as PC
+from noise_robust_vit_amd import patch_convnet as P
 
-from noise_robust_vit_amd import patch_convnet as P  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIX = os.path.join(ROOT, "tests", "golden", "patchconvnet_small.npz")
+FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "patchconvnet_small.npz")
 NEW = ("nrv_dwconv3x3_fwd", "nrv_dwconv3x3_bwd_workspace", "nrv_dwconv3x3_bwd", "nrv_se_fwd", "nrv_se_apply", "nrv_se_bwd_workspace",
        "nrv_se_bwd", "nrv_ls_add_f32", "nrv_ls_bwd_workspace", "nrv_ls_bwd", "nrv_dgelu_rows", "nrv_cls_attn_fwd", "nrv_cls_attn_bwd")
 
@@ -37,41 +32,16 @@ def test_package_exports_patch_convnet():
 @pytest.mark.parametrize("case", list(PF.CASES))
 def test_restatement_matches_reference_fixture(fx, case):
     m = PF.build(P, case)
-    w = PF.weights(m, 3)
-    m.load_state_dict(w, strict=True)
-    tree = PF.unpack_tree(fx, case)
-    assert list(tree) == list(m.state_dict())
-    for k, (shape, s) in tree.items():
-        assert tuple(m.state_dict()[k].shape) == shape, k
-        assert abs(float(w[k].double().sum()) - s) <= 1e-9 * max(1.0, abs(s)), k
-    img, y = PF.inputs(case)
-    logits, loss, grads = R.pcn_loss_and_grads(m, img, y)
-    ref = PF.unpack(fx, case + ".logits")
-    assert float((logits - ref).abs().max()) <= 2e-3 * float(ref.abs().max())
-    assert abs(loss.item() - float(fx[case + ".loss"])) < 1e-4
-    if m.training:
-        G = PF.unpack_grads(fx, case)
-        assert sorted(G) == sorted(grads)
-        for k, g in G.items():
-            a = PF.grad_sample(k, grads[k])
-            assert float((a - g).norm() / (g.norm() + 1e-12)) < 2e-3, k
+    PC.check_keys_and_sums(m, PF.weights(m, 3), fx, case, rtol=1e-9)
+    PC.check_restatement(R.pcn_loss_and_grads(m, *PF.inputs(case)), fx, case, m.training, loss_tol=1e-4, grad_tol=2e-3)
 
 
 @pytest.mark.parametrize("name", PF.BUILDERS)
 def test_seeded_builders_match_reference(fx, name):
     torch.manual_seed(0)
-    m = getattr(P, name)(num_classes=100)
-    sd = m.state_dict()
-    tree = PF.unpack_tree(fx, name)
-    assert list(tree) == list(sd)
-    for k, (shape, s) in tree.items():
-        assert tuple(sd[k].shape) == shape, k
-        v = float(sd[k].double().sum())
-        assert abs(v - s) <= 1e-6 * max(1.0, abs(s)), (k, v, s)
-    n = sum(p.numel() for p in m.parameters())
-    assert n == int(fx[name + ".nparams"])
+    PC.check_seeded_init(getattr(P, name)(num_classes=100), fx, name, rtol=1e-6, atol=0.0)
     if name in PF.NPARAMS:
-        assert n == PF.NPARAMS[name]
+        assert int(fx[name + ".nparams"]) == PF.NPARAMS[name]
 
 
 def test_robust_constructs_with_the_same_state_dict_and_refuses_forward():
@@ -175,15 +145,4 @@ def test_trunc_normal_draws_like_the_reference():
 
 
 def test_abi17_prototypes_in_header_binding_and_exports():
-    from noise_robust_vit_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "nrv.h")).read()
-    assert re.search(r"#define NRV_ABI_VERSION 19\b", hdr) and _lib.ABI_VERSION == 19
-    for name in NEW:
-        assert re.search(r"\b" + name + r"\s*\(", hdr), name
-        assert name in _lib.SIGNATURES, name
-    from noise_robust_vit_amd import build
-    import ctypes
-    lib = ctypes.CDLL(build.build())
-    for name in NEW:
-        assert hasattr(lib, name), name
-    assert lib.nrv_abi_version() == 19
+    PC.check_prototypes(NEW, abi=19)

@@ -4,17 +4,15 @@ new C-ABI prototypes with their shape / pointer / alignment answers.  No GPU."""
 import ctypes
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import pit_fixture as PF  # noqa: E402
-import pit_ref as R  # noqa: E402
-
-from noise_robust_vit_amd import pit as V  # noqa: E402
+import pit_fixture as PF
+import pit_ref as R
+import port_checks as PC
+from noise_robust_vit_amd import pit as V
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIX = os.path.join(ROOT, "tests", "golden", "pit_small.npz")
@@ -31,23 +29,6 @@ def fx():
 def lib():
     from noise_robust_vit_amd import _lib, build
     return _lib.bind(build.build())
-
-
-def _rel(a, b):
-    a, b = a.detach().float().reshape(-1), b.detach().float().reshape(-1)
-    return float((a - b).norm() / (b.norm() + 1e-30))
-
-
-class _FakeCuda(torch.Tensor):
-    """A CPU tensor that says it is on the device: the refusals under test come before any kernel."""
-
-    @property
-    def is_cuda(self):
-        return True
-
-
-def _fake_cuda(t):
-    return t.as_subclass(_FakeCuda)
 
 
 def test_public_interface():
@@ -71,17 +52,7 @@ def test_public_interface():
 @pytest.mark.parametrize("case", list(PF.CASES))
 def test_module_tree_and_keys(fx, case):
     m = PF.build(V, case)
-    tree = PF.unpack_tree(fx, case)
-    sd = m.state_dict()
-    assert list(sd.keys()) == list(tree.keys())
-    for k, (shape, _) in tree.items():
-        assert tuple(sd[k].shape) == shape, k
-    assert [n for n, _ in m.named_modules()] == [str(n) for n in fx[case + ".modules"]]
-    # the fixture weights load strictly (a reference-shaped dict) and sum to what the reference side saw
-    w = PF.weights(m, 3)
-    m.load_state_dict(w, strict=True)
-    for k, (_, s) in tree.items():
-        assert abs(float(m.state_dict()[k].double().sum()) - s) <= 1e-6 * max(1.0, abs(s)), k
+    PC.check_tree_and_keys(m, PF.weights(m, 3), fx, case)
 
 
 def test_key_names():
@@ -101,32 +72,14 @@ def test_key_names():
 @pytest.mark.parametrize("name,cfg", [("small", PF.SMALL), ("full", PF.FULL)])
 def test_seeded_init_matches_reference(fx, name, cfg):
     torch.manual_seed(0)
-    m = V.PiT(**cfg)
-    tree = PF.unpack_tree(fx, name)
-    sd = m.state_dict()
-    assert list(sd.keys()) == list(tree.keys())
-    assert sum(p.numel() for p in m.parameters()) == int(fx[name + ".nparams"])
-    for k, (shape, s) in tree.items():
-        assert tuple(sd[k].shape) == shape, k
-        assert abs(float(sd[k].double().sum()) - s) <= 1e-9 * max(1.0, abs(s)) + 1e-6, k
+    PC.check_seeded_init(V.PiT(**cfg), fx, name)
 
 
 @pytest.mark.parametrize("case", list(PF.CASES))
 def test_restatement_reproduces_the_reference(fx, case):
     m = PF.build(V, case)
     m.load_state_dict(PF.weights(m, 3), strict=True)
-    img, y = PF.inputs(case)
-    logits, loss, grads = R.pit_loss_and_grads(m, img, y)
-    ref = PF.unpack(fx, case + ".logits")
-    err = float((logits - ref).abs().max() / ref.abs().max())
-    print(case, "logits max-abs err / max-abs", err)
-    assert err <= 2e-3
-    assert abs(loss.item() - float(fx[case + ".loss"])) <= 2e-3
-    if m.training:
-        rg = PF.unpack_grads(fx, case)
-        assert set(rg) == set(grads)
-        for k, g in grads.items():
-            assert _rel(PF.grad_sample(k, g), rg[k]) <= 5e-3, k
+    PC.check_restatement(R.pit_loss_and_grads(m, *PF.inputs(case)), fx, case, m.training)
 
 
 def test_the_real_grid_crosses_the_attention_kernels():
@@ -150,21 +103,21 @@ def test_refused_configurations():
     img = torch.zeros(1, 3, 32, 32)
     for kw in (dict(dropout=0.1), dict(emb_dropout=0.1)):
         with pytest.raises(NotImplementedError):
-            V.PiT(**dict(base, **kw)).train()(_fake_cuda(img))
+            V.PiT(**dict(base, **kw)).train()(PC.fake_cuda(img))
     with pytest.raises(NotImplementedError):
-        V.PiT(**base)(_fake_cuda(torch.zeros(1, 3, 32, 24)))              # not square
+        V.PiT(**base)(PC.fake_cuda(torch.zeros(1, 3, 32, 24)))              # not square
     with pytest.raises(NotImplementedError):
-        V.PiT(**base)(_fake_cuda(torch.zeros(1, 3, 40, 40)))              # 81 patches, the table holds 49
+        V.PiT(**base)(PC.fake_cuda(torch.zeros(1, 3, 40, 40)))              # 81 patches, the table holds 49
     from noise_robust_vit_amd.encoder import record_attention
     with record_attention([]):
         with pytest.raises(NotImplementedError):
-            V.PiT(**base)(_fake_cuda(img))
+            V.PiT(**base)(PC.fake_cuda(img))
     t, pool = V.Transformer(32, 1, 2, 32, 64), V.Pool(32)
     for mod in (t, pool):
         with pytest.raises(NotImplementedError):
-            mod(_fake_cuda(torch.zeros(1, 13, 32)))                       # 12 patch tokens: no square grid
+            mod(PC.fake_cuda(torch.zeros(1, 13, 32)))                       # 12 patch tokens: no square grid
     with pytest.raises(NotImplementedError):
-        V.Transformer(32, 1, 2, 32, 64, dropout=0.1).train()(_fake_cuda(torch.zeros(1, 10, 32)))
+        V.Transformer(32, 1, 2, 32, 64, dropout=0.1).train()(PC.fake_cuda(torch.zeros(1, 10, 32)))
     for holder in (t.layers[0][0], t.layers[0][0].fn, t.layers[0][1].fn, pool.downsample):
         with pytest.raises(NotImplementedError):
             holder(torch.zeros(1, 10, 32))                                # holders: a stage and a Pool run as a whole
@@ -176,20 +129,7 @@ def test_refused_configurations():
 
 
 def test_new_prototypes_are_declared_bound_and_exported():
-    from noise_robust_vit_amd import _lib, build
-    text = open(os.path.join(ROOT, "include", "nrv.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    handle = ctypes.CDLL(build.build())
-    for name in NEW:
-        assert re.search(r"\b" + name + r"\s*\(", code), name
-        assert name in _lib.SIGNATURES, name
-        assert hasattr(handle, name), name
-    assert handle.nrv_abi_version() == 19 == _lib.ABI_VERSION
-    assert re.search(r"#define\s+NRV_ABI_VERSION\s+19\b", text)
-    assert "nrv_pit.hip" in build.SOURCES
-    from noise_robust_vit_amd import kernels as K
-    for name in ("pool_dwconv_fwd", "pool_dwconv_bwd", "unfold_patches"):
-        assert callable(getattr(K, name)), name
+    PC.check_prototypes(NEW, abi=19, source="nrv_pit.hip", wrappers=("pool_dwconv_fwd", "pool_dwconv_bwd", "unfold_patches"))
 
 
 def test_pool_entry_points_answer_without_a_device(lib):

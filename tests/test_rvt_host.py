@@ -3,18 +3,15 @@
 tables against stored entries, and the new C-ABI prototypes.  No GPU."""
 import ctypes
 import os
-import re
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import rvt_fixture as RF  # noqa: E402
-import rvt_ref as R  # noqa: E402
-
-from noise_robust_vit_amd import rvt as V  # noqa: E402
+import port_checks as PC
+import rvt_fixture as RF
+import rvt_ref as R
+from noise_robust_vit_amd import rvt as V
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIX = os.path.join(ROOT, "tests", "golden", "rvt_small.npz")
@@ -25,11 +22,6 @@ NEW = ["nrv_rotary_fwd", "nrv_rotary_bwd", "nrv_dwconv_fwd", "nrv_dwconv_bwd_wor
 @pytest.fixture(scope="module")
 def fx():
     return np.load(FIX)
-
-
-def _rel(a, b):
-    a, b = a.detach().float().reshape(-1), b.detach().float().reshape(-1)
-    return float((a - b).norm() / (b.norm() + 1e-30))
 
 
 def test_public_interface():
@@ -48,17 +40,7 @@ def test_public_interface():
 @pytest.mark.parametrize("case", list(RF.CASES))
 def test_module_tree_and_keys(fx, case):
     m = RF.build(V, case)
-    tree = RF.unpack_tree(fx, case)
-    sd = m.state_dict()
-    assert list(sd.keys()) == list(tree.keys())
-    for k, (shape, _) in tree.items():
-        assert tuple(sd[k].shape) == shape, k
-    assert [n for n, _ in m.named_modules()] == [str(n) for n in fx[case + ".modules"]]
-    # the fixture weights load strictly (a reference-shaped dict) and sum to what the reference side saw
-    w = RF.weights(m, 3)
-    m.load_state_dict(w, strict=True)
-    for k, (_, s) in tree.items():
-        assert abs(float(m.state_dict()[k].double().sum()) - s) <= 1e-6 * max(1.0, abs(s)), k
+    PC.check_tree_and_keys(m, RF.weights(m, 3), fx, case)
 
 
 def test_key_names_of_the_query_projection():
@@ -75,32 +57,14 @@ def test_key_names_of_the_query_projection():
 @pytest.mark.parametrize("name,cfg", [("small", RF.SMALL), ("full", RF.FULL)])
 def test_seeded_init_matches_reference(fx, name, cfg):
     torch.manual_seed(0)
-    m = V.RvT(**cfg)
-    tree = RF.unpack_tree(fx, name)
-    sd = m.state_dict()
-    assert list(sd.keys()) == list(tree.keys())
-    assert sum(p.numel() for p in m.parameters()) == int(fx[name + ".nparams"])
-    for k, (shape, s) in tree.items():
-        assert tuple(sd[k].shape) == shape, k
-        assert abs(float(sd[k].double().sum()) - s) <= 1e-9 * max(1.0, abs(s)) + 1e-6, k
+    PC.check_seeded_init(V.RvT(**cfg), fx, name)
 
 
 @pytest.mark.parametrize("case", list(RF.CASES))
 def test_restatement_reproduces_the_reference(fx, case):
     m = RF.build(V, case)
     m.load_state_dict(RF.weights(m, 3), strict=True)
-    img, y = RF.inputs(case)
-    logits, loss, grads = R.rvt_loss_and_grads(m, img, y)
-    ref = RF.unpack(fx, case + ".logits")
-    err = float((logits - ref).abs().max() / ref.abs().max())
-    print(case, "logits max-abs err / max-abs", err)
-    assert err <= 2e-3
-    assert abs(loss.item() - float(fx[case + ".loss"])) <= 2e-3
-    if m.training:
-        rg = RF.unpack_grads(fx, case)
-        assert set(rg) == set(grads)
-        for k, g in grads.items():
-            assert _rel(RF.grad_sample(k, g), rg[k]) <= 5e-3, k
+    PC.check_restatement(R.rvt_loss_and_grads(m, *RF.inputs(case)), fx, case, m.training)
 
 
 @pytest.mark.parametrize("i", range(len(RF.ROTARY_PROBES)))
@@ -132,16 +96,16 @@ def test_refused_configurations():
     img = torch.zeros(1, 3, 48, 48)
     for kw in (dict(dropout=0.1), dict(emb_dropout=0.1)):
         with pytest.raises(NotImplementedError):
-            V.RvT(**dict(base, **kw)).train()(_fake_cuda(img))
+            V.RvT(**dict(base, **kw)).train()(PC.fake_cuda(img))
     with pytest.raises(NotImplementedError):
-        V.RvT(**base)(_fake_cuda(torch.zeros(1, 3, 48, 40)))
+        V.RvT(**base)(PC.fake_cuda(torch.zeros(1, 3, 48, 40)))
     from noise_robust_vit_amd.encoder import record_attention
     with record_attention([]):
         with pytest.raises(NotImplementedError):
-            V.RvT(**base)(_fake_cuda(img))
+            V.RvT(**base)(PC.fake_cuda(img))
     t = V.Transformer(64, 1, 2, 32, 96, 48)
     with pytest.raises(NotImplementedError):
-        t(_fake_cuda(torch.zeros(1, 13, 64)), fmap_dims={'h': 3, 'w': 4})
+        t(PC.fake_cuda(torch.zeros(1, 13, 64)), fmap_dims={'h': 3, 'w': 4})
     with pytest.raises(NotImplementedError):
         t.layers[0][0].fn(torch.zeros(1, 10, 64))                     # a holder: the layer runs as a whole
     from noise_robust_vit_amd._lib import NrvError
@@ -149,32 +113,9 @@ def test_refused_configurations():
         V.RvT(**base)(img)                                            # CPU tensors: no fallback
 
 
-class _FakeCuda(torch.Tensor):
-    """A CPU tensor that says it is on the device: the refusals under test come before any kernel."""
-
-    @property
-    def is_cuda(self):
-        return True
-
-
-def _fake_cuda(t):
-    return t.as_subclass(_FakeCuda)
-
-
 def test_new_prototypes_are_declared_bound_and_exported():
-    from noise_robust_vit_amd import _lib, build
-    text = open(os.path.join(ROOT, "include", "nrv.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    handle = ctypes.CDLL(build.build())
-    for name in NEW:
-        assert re.search(r"\b" + name + r"\s*\(", code), name
-        assert name in _lib.SIGNATURES, name
-        assert hasattr(handle, name), name
-    assert handle.nrv_abi_version() == 19 == _lib.ABI_VERSION
-    assert "nrv_rvt.hip" in build.SOURCES
-    from noise_robust_vit_amd import kernels as K
-    for name in ("rotary_fwd", "rotary_bwd", "dwconv_fwd", "dwconv_bwd", "geglu_fwd", "geglu_bwd"):
-        assert callable(getattr(K, name)), name
+    PC.check_prototypes(NEW, abi=19, source="nrv_rvt.hip",
+                        wrappers=("rotary_fwd", "rotary_bwd", "dwconv_fwd", "dwconv_bwd", "geglu_fwd", "geglu_bwd"))
 
 
 def test_shape_errors_come_back_before_any_launch():

@@ -2,23 +2,19 @@
 tests/t2t_ref.py: logits, loss and every parameter's gradient for each fixture case; eval mode; Trainer.step and Trainer.capture;
 reruns; the kernels the 224-px model launches.
 
-Bounds follow test_cait_gpu.py: the HIP result's rel-L2 to the fp32 restatement may be at most twice the rel-L2 of the same
-restatement under bf16 autocast plus 1e-2, per logits tensor and per parameter gradient; both restatements run on the same GPU
-in the same test.  A gradient that vanishes in the restatement (abs max < 1e-4) is checked to vanish in the HIP result, and
-nothing else is left out."""
+The bound is port_checks.judge's, with both restatements (fp32, bf16 autocast) on the same GPU in the same test.  A gradient
+that vanishes in the restatement (abs max < 1e-4) is checked to vanish in the HIP result, and nothing else is left out."""
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import t2t_fixture as TF  # noqa: E402
-import t2t_ref as R  # noqa: E402
-
-from noise_robust_vit_amd import kernels as K  # noqa: E402
-from noise_robust_vit_amd import t2t as T  # noqa: E402
+import port_checks as PC
+import t2t_fixture as TF
+import t2t_ref as R
+from noise_robust_vit_amd import kernels as K
+from noise_robust_vit_amd import t2t as T
 
 pytestmark = pytest.mark.gpu
 FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "t2t_small.npz")
@@ -34,42 +30,8 @@ def fx():
     return np.load(FIX)
 
 
-def _rel(a, b):
-    a, b = a.detach().float().cpu().reshape(-1), b.detach().float().cpu().reshape(-1)
-    return float((a - b).norm() / (b.norm() + 1e-30))
-
-
-def _hip(model, x, y):
-    model.zero_grad(set_to_none=True)
-    logits = model(x)
-    loss = torch.nn.functional.cross_entropy(logits, y)
-    if model.training:
-        loss.backward()
-    return logits.detach(), loss.detach(), {k: p.grad for k, p in model.named_parameters()}
-
-
-def _compare(model, x, y, fixture=None):
-    logits, loss, grads = _hip(model, x, y)
-    l32, s32, g32 = R.t2t_loss_and_grads(model, x, y)
-    l16, _, g16 = R.t2t_loss_and_grads(model, x, y, autocast=True)
-    bound = 2 * _rel(l16, l32) + 1e-2
-    print(f"logits rel {_rel(logits, l32):.3e} bound {bound:.3e}; loss {loss.item():.5f} vs {s32.item():.5f}")
-    assert _rel(logits, l32) <= bound, (_rel(logits, l32), bound)
-    assert abs(loss.item() - s32.item()) <= 2e-2 * max(1.0, abs(s32.item()))
-    if fixture is not None:
-        fx, case = fixture
-        assert _rel(logits, TF.unpack(fx, case + ".logits")) <= bound
-    if model.training:
-        assert set(grads) == set(g32)
-        for k, g in grads.items():
-            assert g is not None, k
-            if float(g32[k].abs().max()) < 1e-4:
-                assert float(g.abs().max()) < 1e-4, k
-                continue
-            b = 2 * _rel(g16[k], g32[k]) + 1e-2
-            print(f"{k}: rel {_rel(g, g32[k]):.3e} bound {b:.3e}")
-            assert _rel(g, g32[k]) <= b, (k, _rel(g, g32[k]), b)
-    return logits, grads
+def _compare(model, x, y, **rules):
+    return PC.compare(model, x, y, lambda m, x, y, low: R.t2t_loss_and_grads(m, x, y, autocast=low), **rules)
 
 
 @pytest.mark.parametrize("case", list(TF.CASES))
@@ -78,7 +40,7 @@ def test_fixture_parity(dev, fx, case):
     m.load_state_dict(TF.weights(m, 3))
     m = m.to(dev)
     img, y = TF.inputs(case)
-    _compare(m, img.to(dev), y.to(dev), fixture=(fx, case))
+    _compare(m, img.to(dev), y.to(dev), fixture_logits=TF.unpack(fx, case + ".logits"))
 
 
 def _model(dev, cfg, **kw):
@@ -104,13 +66,7 @@ def test_eval_mode_is_deterministic(dev):
 
 @pytest.mark.parametrize("robust", [False, True])
 def test_reruns_are_bit_identical(dev, robust):
-    m = _model(dev, TF.SMALL, robust=robust).train()
-    x, y = _batch(dev, 2)
-    runs = []
-    for _ in range(2):
-        lg, _, g = _hip(m, x, y)
-        runs.append([lg] + [t.clone() for t in g.values()])
-    assert all(torch.equal(a, b) for a, b in zip(*runs))
+    PC.check_reruns_bit_identical(_model(dev, TF.SMALL, robust=robust).train(), *_batch(dev, 2))
 
 
 def test_224_runs_the_fused_wide_head_path(dev):
@@ -118,7 +74,7 @@ def test_224_runs_the_fused_wide_head_path(dev):
     (784 tokens, 1323 in 1328): no [3136, 3136] matrix is formed."""
     m = _model(dev, dict(TF.SMALL, image_size=224, depth=1)).train()
     x, y = _batch(dev, 1, 224)
-    _hip(m, x, y)                                  # warm
+    PC.hip_step(m, x, y)                           # warm
     seen = []
     orig = K.bgemm
 
@@ -129,7 +85,7 @@ def test_224_runs_the_fused_wide_head_path(dev):
     K.bgemm = spy
     try:
         with K.LaunchProfile() as prof:
-            _hip(m, x, y)
+            PC.hip_step(m, x, y)
     finally:
         K.bgemm = orig
     names = prof.summary()
@@ -141,22 +97,9 @@ def test_224_runs_the_fused_wide_head_path(dev):
 
 
 def test_trainer_step_and_capture(dev):
-    from noise_robust_vit_amd.train import TrainConfig, Trainer
-    a = _model(dev, TF.SMALL).train()
-    b = _model(dev, TF.SMALL).train()
-    cfg = TrainConfig(lr=1e-3)
-    ta, tb = Trainer(a, cfg), Trainer(b, cfg)
     x, y = _batch(dev, 8, seed=11)
-    ta.capture(x, y)
-    la = [ta.step(x, y) for _ in range(3)]
-    lb = [tb.step(x, y) for _ in range(3)]
-    assert all(torch.equal(u, v) for u, v in zip(la, lb)), (la, lb)
-    for (n, p), q in zip(a.named_parameters(), b.parameters()):
-        assert torch.equal(p, q), n
-    losses = [lb[-1].item()] + [tb.step(x, y).item() for _ in range(20)]
-    assert losses[-1] < losses[0], losses
-    ev = tb.eval_step(x, y)
-    assert torch.isfinite(ev).all()
+    tb = PC.check_eager_vs_captured(lambda: _model(dev, TF.SMALL).train(), x, y)
+    assert torch.isfinite(tb.eval_step(x, y)).all()
 
 
 def test_trainer_robust_loss_falls(dev):
@@ -174,10 +117,7 @@ def test_width_27_runs_the_head_dim_32_kernels(dev):
     cfg = dict(TF.SMALL, depth=1, t2t_layers=((3, 2), (3, 2)))
     m = _model(dev, cfg).train()
     x, y = _batch(dev, 2)
-    _hip(m, x, y)
-    with K.LaunchProfile() as prof:
-        _hip(m, x, y)
-    names = prof.summary()
+    names = PC.profiled_step(m, x, y)
     assert names["attn_fwd"]["launches"] == 2 and names["attn_bwd"]["launches"] == 2, sorted(names)
     assert "bgemm" not in names and "attn_wide_fwd" not in names, sorted(names)
     _compare(m, x, y)
@@ -209,5 +149,5 @@ def test_stage_layer_keeps_the_pad_columns_zero(dev, C, N, kind):
     xr = x.detach()[:, :C].reshape(B, N, C).clone().requires_grad_(True)
     ref = R._layer(P, "layers.0.", xr, 1, C ** -0.5, False)
     (ref * w.to(dev)[:, :C].reshape(B, N, C)).sum().backward()
-    assert _rel(y[:, :C], ref.reshape(B * N, C)) <= 2e-2
-    assert _rel(x.grad[:, :C], xr.grad.reshape(B * N, C)) <= 3e-2
+    assert PC.rel(y[:, :C], ref.reshape(B * N, C)) <= 2e-2
+    assert PC.rel(x.grad[:, :C], xr.grad.reshape(B * N, C)) <= 3e-2

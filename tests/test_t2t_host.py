@@ -3,18 +3,15 @@
 new C-ABI prototypes.  No GPU."""
 import ctypes
 import os
-import re
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import t2t_fixture as TF  # noqa: E402
-import t2t_ref as R  # noqa: E402
-
-from noise_robust_vit_amd import t2t as T  # noqa: E402
+import port_checks as PC
+import t2t_fixture as TF
+import t2t_ref as R
+from noise_robust_vit_amd import t2t as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIX = os.path.join(ROOT, "tests", "golden", "t2t_small.npz")
@@ -25,11 +22,6 @@ NEW = ["nrv_soft_split_fwd", "nrv_soft_split_bwd", "nrv_layernorm_pad_fwd", "nrv
 @pytest.fixture(scope="module")
 def fx():
     return np.load(FIX)
-
-
-def _rel(a, b):
-    a, b = a.detach().float().reshape(-1), b.detach().float().reshape(-1)
-    return float((a - b).norm() / (b.norm() + 1e-30))
 
 
 def test_public_interface():
@@ -44,48 +36,20 @@ def test_public_interface():
 @pytest.mark.parametrize("case", list(TF.CASES))
 def test_module_tree_and_keys(fx, case):
     m = TF.build(T, case)
-    tree = TF.unpack_tree(fx, case)
-    sd = m.state_dict()
-    assert list(sd.keys()) == list(tree.keys())
-    for k, (shape, _) in tree.items():
-        assert tuple(sd[k].shape) == shape, k
-    assert [n for n, _ in m.named_modules()] == [str(n) for n in fx[case + ".modules"]]
-    # the fixture weights load strictly (a reference-shaped dict) and sum to what the reference side saw
-    w = TF.weights(m, 3)
-    m.load_state_dict(w, strict=True)
-    for k, (_, s) in tree.items():
-        assert abs(float(m.state_dict()[k].double().sum()) - s) <= 1e-6 * max(1.0, abs(s)), k
+    PC.check_tree_and_keys(m, TF.weights(m, 3), fx, case)
 
 
 @pytest.mark.parametrize("name,cfg", [("small", TF.SMALL), ("full", TF.FULL)])
 def test_seeded_init_matches_reference(fx, name, cfg):
     torch.manual_seed(0)
-    m = T.T2TViT(**cfg)
-    tree = TF.unpack_tree(fx, name)
-    sd = m.state_dict()
-    assert list(sd.keys()) == list(tree.keys())
-    assert sum(p.numel() for p in m.parameters()) == int(fx[name + ".nparams"])
-    for k, (shape, s) in tree.items():
-        assert tuple(sd[k].shape) == shape, k
-        assert abs(float(sd[k].double().sum()) - s) <= 1e-9 * max(1.0, abs(s)) + 1e-6, k
+    PC.check_seeded_init(T.T2TViT(**cfg), fx, name)
 
 
 @pytest.mark.parametrize("case", list(TF.CASES))
 def test_restatement_reproduces_the_reference(fx, case):
     m = TF.build(T, case)
     m.load_state_dict(TF.weights(m, 3), strict=True)
-    img, y = TF.inputs(case)
-    logits, loss, grads = R.t2t_loss_and_grads(m, img, y)
-    ref = TF.unpack(fx, case + ".logits")
-    err = float((logits - ref).abs().max() / ref.abs().max())
-    print(case, "logits max-abs err / max-abs", err)
-    assert err <= 2e-3
-    assert abs(loss.item() - float(fx[case + ".loss"])) <= 2e-3
-    if m.training:
-        rg = TF.unpack_grads(fx, case)
-        assert set(rg) == set(grads)
-        for k, g in grads.items():
-            assert _rel(TF.grad_sample(k, g), rg[k]) <= 5e-3, k
+    PC.check_restatement(R.t2t_loss_and_grads(m, *TF.inputs(case)), fx, case, m.training)
 
 
 def test_refused_configurations():
@@ -122,16 +86,7 @@ def test_user_transformer_is_used_as_given():
 
 
 def test_new_prototypes_are_declared_bound_and_exported():
-    from noise_robust_vit_amd import _lib, build
-    text = open(os.path.join(ROOT, "include", "nrv.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    handle = ctypes.CDLL(build.build())
-    for name in NEW:
-        assert re.search(r"\b" + name + r"\s*\(", code), name
-        assert name in _lib.SIGNATURES, name
-        assert hasattr(handle, name), name
-    assert handle.nrv_abi_version() == 19 == _lib.ABI_VERSION
-    assert "nrv_t2t.hip" in build.SOURCES
+    PC.check_prototypes(NEW, abi=19, source="nrv_t2t.hip")
 
 
 def test_shape_errors_come_back_before_any_launch():

@@ -4,16 +4,14 @@ and the plan query.  No GPU."""
 import ctypes
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import twins_fixture as TF  # noqa: E402
-
-from noise_robust_vit_amd import twins_svt as V  # noqa: E402
+import port_checks as PC
+import twins_fixture as TF
+from noise_robust_vit_amd import twins_svt as V
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIX = os.path.join(ROOT, "tests", "golden", "twins_small.npz")
@@ -31,18 +29,6 @@ def fx():
 def lib():
     from noise_robust_vit_amd import _lib, build
     return _lib.bind(build.build())
-
-
-class _FakeCuda(torch.Tensor):
-    """A CPU tensor that says it is on the device: the refusals under test come before any kernel."""
-
-    @property
-    def is_cuda(self):
-        return True
-
-
-def _fake_cuda(t):
-    return t.as_subclass(_FakeCuda)
 
 
 def test_public_interface():
@@ -68,17 +54,7 @@ def test_public_interface():
 @pytest.mark.parametrize("case", list(TF.CASES))
 def test_module_tree_and_keys(fx, case):
     m = TF.build(V, case)
-    tree = TF.unpack_tree(fx, case)
-    sd = m.state_dict()
-    assert list(sd.keys()) == list(tree.keys())
-    for k, (shape, _) in tree.items():
-        assert tuple(sd[k].shape) == shape, k
-    assert [n for n, _ in m.named_modules()] == [str(n) for n in fx[case + ".modules"]]
-    # the fixture weights load strictly (a reference-shaped dict) and sum to what the reference side saw
-    w = TF.weights(m, 3)
-    m.load_state_dict(w, strict=True)
-    for k, (_, s) in tree.items():
-        assert abs(float(m.state_dict()[k].double().sum()) - s) <= 1e-6 * max(1.0, abs(s)), k
+    PC.check_tree_and_keys(m, TF.weights(m, 3), fx, case)
 
 
 def test_key_names_and_shapes():
@@ -101,14 +77,7 @@ def test_key_names_and_shapes():
 @pytest.mark.parametrize("name,cfg", [("small", TF.SMALL), ("full", TF.FULL)])
 def test_seeded_init_matches_reference(fx, name, cfg):
     torch.manual_seed(0)
-    m = V.TwinsSVT(**cfg)
-    tree = TF.unpack_tree(fx, name)
-    sd = m.state_dict()
-    assert list(sd.keys()) == list(tree.keys())
-    assert sum(p.numel() for p in m.parameters()) == int(fx[name + ".nparams"])
-    for k, (shape, s) in tree.items():
-        assert tuple(sd[k].shape) == shape, k
-        assert abs(float(sd[k].double().sum()) - s) <= 1e-9 * max(1.0, abs(s)) + 1e-6, k
+    PC.check_seeded_init(V.TwinsSVT(**cfg), fx, name)
 
 
 def test_refused_configurations():
@@ -119,22 +88,22 @@ def test_refused_configurations():
             V.TwinsSVT(**dict(base, **kw))
     img = torch.zeros(1, 3, 56, 56)
     with pytest.raises(NotImplementedError):
-        V.TwinsSVT(**dict(base, dropout=0.1)).train()(_fake_cuda(img))
+        V.TwinsSVT(**dict(base, dropout=0.1)).train()(PC.fake_cuda(img))
     with pytest.raises(NotImplementedError):
-        V.TwinsSVT(**base)(_fake_cuda(torch.zeros(1, 3, 56, 28)))         # not square
+        V.TwinsSVT(**base)(PC.fake_cuda(torch.zeros(1, 3, 56, 28)))         # not square
     with pytest.raises(NotImplementedError):
-        V.TwinsSVT(**base)(_fake_cuda(torch.zeros(1, 3, 48, 48)))         # a 24 x 24 map: windows of 7 do not tile it
+        V.TwinsSVT(**base)(PC.fake_cuda(torch.zeros(1, 3, 48, 48)))         # a 24 x 24 map: windows of 7 do not tile it
     with pytest.raises(NotImplementedError):
-        V.TwinsSVT(**dict(base, s1_local_patch_size=4, s1_global_k=5))(_fake_cuda(img))     # 28 x 28: k = 5 does not tile it
+        V.TwinsSVT(**dict(base, s1_local_patch_size=4, s1_global_k=5))(PC.fake_cuda(img))     # 28 x 28: k = 5 does not tile it
     from noise_robust_vit_amd.encoder import record_attention
     with record_attention([]):
         with pytest.raises(NotImplementedError):
-            V.TwinsSVT(**base)(_fake_cuda(img))
+            V.TwinsSVT(**base)(PC.fake_cuda(img))
     t = V.Transformer(16, 1)
     with pytest.raises(NotImplementedError):
-        t(_fake_cuda(torch.zeros(1, 16, 7, 14)))
+        t(PC.fake_cuda(torch.zeros(1, 16, 7, 14)))
     with pytest.raises(NotImplementedError):
-        V.Transformer(16, 1, dropout=0.1).train()(_fake_cuda(torch.zeros(1, 16, 7, 7)))
+        V.Transformer(16, 1, dropout=0.1).train()(PC.fake_cuda(torch.zeros(1, 16, 7, 7)))
     res = t.layers[0][0]
     for holder in (res, res.fn, res.fn.norm, res.fn.fn, t.layers[0][1].fn.fn, t.layers[0][2].fn.fn, V.PEG(16), V.PEG(16).proj,
                    V.PatchEmbedding(dim=3, dim_out=16, patch_size=2)):
@@ -148,20 +117,8 @@ def test_refused_configurations():
 
 
 def test_new_prototypes_are_declared_bound_and_exported():
-    from noise_robust_vit_amd import _lib, build
-    text = open(os.path.join(ROOT, "include", "nrv.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    handle = ctypes.CDLL(build.build())
-    for name in NEW:
-        assert re.search(r"\b" + name + r"\s*\(", code), name
-        assert name in _lib.SIGNATURES, name
-        assert hasattr(handle, name), name
-    assert handle.nrv_abi_version() == 19 == _lib.ABI_VERSION
-    assert re.search(r"#define\s+NRV_ABI_VERSION\s+19\b", text)
-    assert "nrv_twins.hip" in build.SOURCES
-    from noise_robust_vit_amd import kernels as K
-    for name in ("subattn_fwd", "subattn_bwd", "subattn_plan", "peg_fwd", "peg_bwd"):
-        assert callable(getattr(K, name)), name
+    PC.check_prototypes(NEW, abi=19, source="nrv_twins.hip",
+                        wrappers=("subattn_fwd", "subattn_bwd", "subattn_plan", "peg_fwd", "peg_bwd"))
 
 
 def test_subattn_plan(lib):
@@ -268,8 +225,8 @@ def test_wrappers_refuse_bad_arguments_before_a_launch():
     """kernels.subattn_* / peg_* check dtypes, views and shapes on the host (fake device tensors: nothing is launched)."""
     from noise_robust_vit_amd import kernels as K
     from noise_robust_vit_amd._lib import NrvError
-    q = _fake_cuda(torch.zeros(2 * 49, 512, dtype=torch.bfloat16))
-    kv = _fake_cuda(torch.zeros(2 * 4, 1024, dtype=torch.bfloat16))
+    q = PC.fake_cuda(torch.zeros(2 * 49, 512, dtype=torch.bfloat16))
+    kv = PC.fake_cuda(torch.zeros(2 * 4, 1024, dtype=torch.bfloat16))
     for args in ((q, kv[:, :512], kv[:, 512:], 2, 8, 49, 0, 64), (q, kv[:, :512], kv[:, 512:], 2, 8, 49, 129, 64),
                  (q, kv[:, :512], kv[:, 512:], 2, 8, 49, 4, 48), (q.float(), kv[:, :512], kv[:, 512:], 2, 8, 49, 4, 64),
                  (q, kv[:, :512], kv[:, 512:], 2, 8, 50, 4, 64), (q[:, :256], kv[:, :512], kv[:, 512:], 2, 8, 49, 4, 64)):
@@ -277,11 +234,11 @@ def test_wrappers_refuse_bad_arguments_before_a_launch():
             K.subattn_fwd(*args, 0.125)
     with pytest.raises(NrvError):
         K.subattn_fwd(torch.zeros(98, 512, dtype=torch.bfloat16), kv[:, :512], kv[:, 512:], 2, 8, 49, 4, 64, 0.125)     # CPU tensor
-    x = _fake_cuda(torch.zeros(2 * 15, 40))
+    x = PC.fake_cuda(torch.zeros(2 * 15, 40))
     for w in (torch.zeros(40, 4), torch.zeros(40, 81), torch.zeros(39, 9)):
         with pytest.raises(NrvError):
-            K.peg_fwd(x, _fake_cuda(w), _fake_cuda(torch.zeros(40)), 2, 3, 5)
+            K.peg_fwd(x, PC.fake_cuda(w), PC.fake_cuda(torch.zeros(40)), 2, 3, 5)
     with pytest.raises(NrvError):
-        K.peg_fwd(x, _fake_cuda(torch.zeros(40, 9)), _fake_cuda(torch.zeros(40)), 2, 3, 4)       # 30 rows are not 2 x 3 x 4
+        K.peg_fwd(x, PC.fake_cuda(torch.zeros(40, 9)), PC.fake_cuda(torch.zeros(40)), 2, 3, 4)       # 30 rows are not 2 x 3 x 4
     with pytest.raises(NrvError):
-        K.peg_fwd(_fake_cuda(torch.zeros(30, 36)), _fake_cuda(torch.zeros(36, 9)), _fake_cuda(torch.zeros(36)), 2, 3, 5)   # C % 8
+        K.peg_fwd(PC.fake_cuda(torch.zeros(30, 36)), PC.fake_cuda(torch.zeros(36, 9)), PC.fake_cuda(torch.zeros(36)), 2, 3, 5)   # C % 8

@@ -2,14 +2,16 @@
 
 tests/golden/gen_golden_twins.py loads these into the reference's twins_svt.py modules and stores what the reference computes
 (logits, CE loss, the gradient of every parameter) plus the module trees; the tests load the same tensors into the HIP modules
-and into tests/twins_ref.py.  Seeds, packing and gradient sampling are swin_fixture's.
+and into tests/twins_ref.py.  Seeds, packing and gradient sampling are port_fixture's; the weight recipe is its own (the
+LayerNorm gains `g` are rank 4 and the rule goes by leaf name, not by rank).
 
 The reference's Twins-SVT has no `attend` module to swap, so the robust cases have no fixture: they are compared against the
 restatement only (ROBUST_CASES).
 """
 import torch
 
-from swin_fixture import _gen, grad_index, grad_sample, pack, pack_grads, pack_tree, unpack, unpack_grads, unpack_tree  # noqa: F401
+from port_fixture import (_gen, grad_index, grad_sample, image_inputs, pack, pack_grads, pack_tree, unpack, unpack_grads,  # noqa: F401
+                          unpack_tree)
 
 # 56 px: maps 28 / 14 / 7 / 7; global attention 784 x 16, 196 x 49, 49 x 1, 49 x 49 (queries x keys)
 BASE = dict(num_classes=10,
@@ -59,7 +61,4 @@ def weights(model, seed: int) -> dict:
 
 def inputs(case: str):
     cfg, size, _, B = {**CASES, **ROBUST_CASES}[case]
-    g = _gen(17, "inputs." + case)
-    img = torch.randn(B, 3, size, size, generator=g)
-    y = torch.randint(0, cfg["num_classes"], (B,), generator=g)
-    return img, y
+    return image_inputs(case, B, 3, size, size, cfg["num_classes"])

@@ -45,9 +45,6 @@ Tensor = torch.Tensor
 
 __all__ = ["CaiT", "Transformer", "Attention", "FeedForward", "LayerScale", "PreNorm", "dropout_layers"]
 
-SINKHORN_ITERS = 3                       # SinkhornAttention's default (utils.py:1025-1037)
-
-
 def exists(val):
     return val is not None
 
@@ -67,13 +64,7 @@ def dropout_layers(layers, dropout):
 # ----------------------------------------------------------------------------------------------
 # modules (parameter holders with the reference's names and construction order)
 # ----------------------------------------------------------------------------------------------
-class _Holder(nn.Module):
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError(f"{type(self).__name__} holds parameters only: a CaiT layer runs as one fused HIP schedule, "
-                                  "call the Transformer (or CaiT) that owns it")
-
-
-class LayerScale(_Holder):
+class LayerScale(E.Holder):
     def __init__(self, dim, fn, depth):
         super().__init__()
         if depth <= 18:                  # epsilon detailed in section 2 of the paper (cait.py:39-44)
@@ -86,23 +77,10 @@ class LayerScale(_Holder):
         self.fn = fn
 
 
-class PreNorm(_Holder):
-    def __init__(self, dim, fn):
-        super().__init__()
-        self.norm = nn.LayerNorm(dim)
-        self.fn = fn
+PreNorm, FeedForward = E.PreNorm, E.FeedForward
 
 
-class FeedForward(_Holder):
-    def __init__(self, dim, hidden_dim, dropout=0.0):
-        super().__init__()
-        if dim % 8 or hidden_dim % 8:
-            raise NotImplementedError(f"FeedForward {dim} -> {hidden_dim}: the GEMMs take multiples of 8")
-        self.net = nn.Sequential(nn.Linear(dim, hidden_dim), nn.GELU(), nn.Dropout(dropout), nn.Linear(hidden_dim, dim),
-                                 nn.Dropout(dropout))
-
-
-class Attention(_Holder):
+class Attention(E.Holder):
     """Talking-heads attention (cait.py:76-120); robust=True normalises with SinkhornAttention instead of softmax."""
 
     def __init__(self, dim, heads=8, dim_head=64, dropout=0.0, robust=False):
@@ -164,7 +142,7 @@ class LayerFn(torch.autograd.Function):
         w1d, w2d = w1.detach(), w2.detach()
         if robust:
             T = K.head_mix_fwd(S, w1d)
-            P, lse, avec, bvec = K.sinkhorn_fwd(T, iters=SINKHORN_ITERS)
+            P, lse, avec, bvec = K.sinkhorn_fwd(T, iters=K.SINKHORN_ITERS)
             del T
             A = K.head_mix_fwd(P, w2d, out_dtype=torch.bfloat16)
             stats = (lse, avec, bvec)
@@ -209,7 +187,7 @@ class LayerFn(torch.autograd.Function):
             dP, dw2 = K.head_mix_bwd(dA, P, w2d)
             del dA, P
             T = K.head_mix_fwd(S, w1d)
-            dT = K.sinkhorn_bwd(T, dP, *stats, iters=SINKHORN_ITERS)
+            dT = K.sinkhorn_bwd(T, dP, *stats, iters=K.SINKHORN_ITERS)
             del T, dP
             dS, dw1 = K.head_mix_bwd(dT, S, w1d)
             del dT
@@ -255,11 +233,9 @@ class Transformer(nn.Module):
             ]))
 
     def _check_forward(self, x, context=None) -> None:
-        E.require_cuda(x)
         if context is not None:
-            E.require_cuda(context)
-        if E._RECORDING is not None:
-            raise NotImplementedError("attention-map recording is not implemented for CaiT")
+            E.require_cuda(context)                  # ahead of the recording refusal, as a CPU x is
+        E.require_run(x, "CaiT")
         if self.training and self.dropout > 0:
             raise NotImplementedError("dropout > 0 in training is not implemented for CaiT (eval mode runs)")
         if x.dim() != 3 or (context is not None and (context.dim() != 3 or context.shape[0] != x.shape[0] or
@@ -295,18 +271,6 @@ class Transformer(nn.Module):
         return self.run(x.to(torch.float32).contiguous().reshape(B * n, D), B, n, c, N).reshape(B, n, D)
 
 
-class _Rearrange(nn.Module):
-    """Placeholder for einops' Rearrange('b c (h p1) (w p2) -> b (h w) (p1 p2 c)') at to_patch_embedding.0 (no parameters; the
-    unfold runs in nrv_patch_unfold)."""
-
-    def __init__(self, patch_size: int):
-        super().__init__()
-        self.patch_size = patch_size
-
-    def extra_repr(self):
-        return f"'b c (h p1) (w p2) -> b (h w) (p1 p2 c)', p1={self.patch_size}, p2={self.patch_size}"
-
-
 class CaiT(nn.Module):
     """cait.py:168-232 with the reference's constructor arguments, plus `robust` (see the module docstring)."""
 
@@ -317,7 +281,8 @@ class CaiT(nn.Module):
         num_patches = (image_size // patch_size) ** 2
         patch_dim = 3 * patch_size ** 2
         self.patch_size = patch_size
-        self.to_patch_embedding = nn.Sequential(_Rearrange(patch_size), nn.Linear(patch_dim, dim))
+        self.to_patch_embedding = nn.Sequential(E.Rearrange('b c (h p1) (w p2) -> b (h w) (p1 p2 c)', p1=patch_size, p2=patch_size),
+                                                nn.Linear(patch_dim, dim))
         self.pos_embedding = nn.Parameter(torch.randn(1, num_patches, dim))
         self.cls_token = nn.Parameter(torch.randn(1, 1, dim))
         self.dropout = nn.Dropout(emb_dropout)
@@ -330,9 +295,7 @@ class CaiT(nn.Module):
         return max(self.patch_transformer.layer_dropout, self.cls_transformer.layer_dropout)
 
     def _check_forward(self, img) -> None:
-        E.require_cuda(img)
-        if E._RECORDING is not None:
-            raise NotImplementedError("attention-map recording is not implemented for CaiT")
+        E.require_run(img, "CaiT")
         if self.training and (self.dropout.p > 0 or self.patch_transformer.dropout > 0 or self.cls_transformer.dropout > 0):
             raise NotImplementedError("dropout / emb_dropout > 0 in training is not implemented for CaiT (eval mode runs)")
         p = self.patch_size

@@ -55,7 +55,6 @@ Tensor = torch.Tensor
 __all__ = ["cct_2", "cct_4", "cct_6", "cct_7", "cct_8", "cct_14", "cct_16", "CCT", "Tokenizer", "TransformerClassifier",
            "TransformerEncoderLayer", "Attention", "DropPath", "sinusoidal_embedding"]
 
-_FUSED_DH = (32, 64, 80, 96, 128)        # nrv_attn_fwd's head dims
 MAX_TOKENS = 4096                         # nrv_seqpool_*'s tokens per sample
 CONV_OUT_F32 = False                      # the conv GEMM writes bf16 rows; nrv_relu_maxpool_fwd takes both
 
@@ -126,9 +125,9 @@ class Attention(nn.Module):
         super().__init__()
         self.heads = num_heads
         head_dim = dim // self.heads
-        if dim % 8 or dim > 4096 or head_dim * num_heads != dim or head_dim not in _FUSED_DH:
+        if dim % 8 or dim > 4096 or head_dim * num_heads != dim or head_dim not in K.ATTN_FUSED_DH:
             raise NotImplementedError(f"Attention dim {dim} / {num_heads} heads: dim % 8 == 0, dim <= 4096 and a head dim of "
-                                      f"{_FUSED_DH} (the attention kernels)")
+                                      f"{K.ATTN_FUSED_DH} (the attention kernels)")
         self.scale = head_dim ** -0.5
         self.robust = bool(robust)
         # dropout on the attention weights inside the fused softmax kernels (kernels.attn_drop_fwd) instead of on a materialised
@@ -267,9 +266,7 @@ class TransformerEncoderLayer(nn.Module):
                 self.linear1.bias, self.norm1.weight, self.norm1.bias, self.linear2.weight, self.linear2.bias]
 
     def forward(self, src, *args, **kwargs):
-        E.require_cuda(src)
-        if E._RECORDING is not None:
-            raise NotImplementedError("attention-map recording is not implemented for CCT")
+        E.require_run(src, "CCT")
         if src.dim() != 3 or src.shape[2] != self.pre_norm.normalized_shape[0] or not 1 <= src.shape[1] <= MAX_TOKENS:
             raise NotImplementedError(f"TransformerEncoderLayer takes [B, n <= {MAX_TOKENS}, {self.pre_norm.normalized_shape[0]}], "
                                       f"got {tuple(src.shape)}")
@@ -303,14 +300,13 @@ class TokenizerFn(torch.autograd.Function):
         for li, (w, (ks, st, pad, relu, pk, ps, pp)) in enumerate(zip(weights, geom)):
             Co = w.shape[0]
             last = li == len(weights) - 1
-            cols = K.conv_unfold(src, B, Cin, H, W, ks, st, pad, nhwc=li > 0)
-            wb, wt = E.conv_images(w, cols.shape[1])
+            cols, wb, wt = E.conv_cols(src, w, B, Cin, H, W, ks, st, pad, li > 0)
             Hc, Wc = K.conv_out_size(H, ks, st, pad), K.conv_out_size(W, ks, st, pad)
             y = K.gemm_nt(cols, wb, out_dtype=torch.float32 if CONV_OUT_F32 else torch.bfloat16)
             x32, src, idx = K.relu_maxpool_fwd(y, B, Hc, Wc, pk, ps, pp, relu=relu, want_f32=last, want_bf16=not last)
             layers.append((cols, wt, idx, (Cin, H, W, Hc, Wc)))
             Cin, H, W = Co, K.maxpool_out_size(Hc, pk, ps, pp), K.maxpool_out_size(Wc, pk, ps, pp)
-        ctx.layers, ctx.B, ctx.geom, ctx.shapes = layers, B, geom, [w.shape for w in weights]
+        ctx.layers, ctx.B, ctx.geom = layers, B, geom
         return x32.reshape(B, H * W, Cin)
 
     @staticmethod
@@ -322,13 +318,10 @@ class TokenizerFn(torch.autograd.Function):
         for li in range(len(layers) - 1, -1, -1):
             cols, wt, idx, (Cin, H, W, Hc, Wc) = layers[li]
             ks, st, pad, _, pk, ps, pp = ctx.geom[li]
-            Co = ctx.shapes[li][0]
             dy = K.relu_maxpool_bwd(dout, idx, B, Hc, Wc, pk, ps, pp)
-            dwi = K.gemm_tn(dy, cols)                                   # [Co, KP] in (ky, kx, c) order
-            grads[li] = dwi[:, :ks * ks * Cin].reshape(Co, ks, ks, Cin).permute(0, 3, 1, 2).contiguous()
+            grads[li] = E.conv_wgrad(dy, cols, Cin, ks)
             if li > 0:
-                dcols = K.gemm_nt(dy, wt, out_dtype=torch.bfloat16)
-                dout = K.conv_fold(dcols, B, Cin, H, W, ks, st, pad)   # the previous pool's dout, fp32 NHWC rows
+                dout = E.conv_dx(dy, wt, B, Cin, H, W, ks, st, pad)    # the previous pool's dout, fp32 NHWC rows
         return (None, None, *grads)
 
 
@@ -521,9 +514,7 @@ class TransformerClassifier(nn.Module):
         return []
 
     def forward(self, x):
-        E.require_cuda(x)
-        if E._RECORDING is not None:
-            raise NotImplementedError("attention-map recording is not implemented for CCT")
+        E.require_run(x, "CCT")
         if self.training and self.dropout.p > 0:
             raise NotImplementedError("dropout_rate > 0 in training is not implemented for CCT (eval mode runs)")
         if x.dim() != 3 or x.shape[2] != self.embedding_dim:
@@ -611,9 +602,7 @@ class CCT(nn.Module):
         return []
 
     def forward(self, x):
-        E.require_cuda(x)
-        if E._RECORDING is not None:
-            raise NotImplementedError("attention-map recording is not implemented for CCT")
+        E.require_run(x, "CCT")
         if x.dim() != 4 or tuple(x.shape[2:]) != self.img_size:
             raise NotImplementedError(f"CCT was built for {self.img_size[0]} x {self.img_size[1]} images, got {tuple(x.shape)}")
         x = self.tokenizer(x)

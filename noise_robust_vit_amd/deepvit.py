@@ -40,53 +40,13 @@ Tensor = torch.Tensor
 
 __all__ = ["DeepViT", "Transformer", "Attention", "FeedForward", "PreNorm", "Residual"]
 
-SINKHORN_ITERS = 3                       # SinkhornAttention's default (utils.py:1025-1037)
-
-
 # ----------------------------------------------------------------------------------------------
 # modules (parameter holders with the reference's names and construction order)
 # ----------------------------------------------------------------------------------------------
-class _Holder(nn.Module):
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError(f"{type(self).__name__} holds parameters only: a DeepViT layer runs as one fused HIP schedule, "
-                                  "call the Transformer (or DeepViT) that owns it")
+PreNorm, FeedForward, Residual = E.PreNorm, E.FeedForward, E.Residual
 
 
-class Residual(_Holder):
-    def __init__(self, fn):
-        super().__init__()
-        self.fn = fn
-
-
-class PreNorm(_Holder):
-    def __init__(self, dim, fn):
-        super().__init__()
-        self.norm = nn.LayerNorm(dim)
-        self.fn = fn
-
-
-class FeedForward(_Holder):
-    def __init__(self, dim, hidden_dim, dropout=0.0):
-        super().__init__()
-        if dim % 8 or hidden_dim % 8:
-            raise NotImplementedError(f"FeedForward {dim} -> {hidden_dim}: the GEMMs take multiples of 8")
-        self.net = nn.Sequential(nn.Linear(dim, hidden_dim), nn.GELU(), nn.Dropout(dropout), nn.Linear(hidden_dim, dim),
-                                 nn.Dropout(dropout))
-
-
-class _Rearrange(nn.Module):
-    """Placeholder for an einops Rearrange (no parameters): the patch unfold runs in nrv_patch_unfold, and the two permutes
-    around the LayerNorm over heads (reattn_norm.0 / .2) are the re-attention kernels' indexing."""
-
-    def __init__(self, pattern: str, **axes):
-        super().__init__()
-        self.pattern, self.axes = pattern, axes
-
-    def extra_repr(self):
-        return ", ".join([repr(self.pattern)] + [f"{k}={v}" for k, v in self.axes.items()])
-
-
-class Attention(_Holder):
+class Attention(E.Holder):
     """Attention with re-attention (deepvit.py:36-81); robust=True normalises with SinkhornAttention instead of softmax."""
 
     def __init__(self, dim, heads=8, dim_head=64, dropout=0.0, robust=False):
@@ -103,7 +63,8 @@ class Attention(_Holder):
         self.to_qkv = nn.Linear(dim, inner_dim * 3, bias=False)
         self.dropout = nn.Dropout(dropout)
         self.reattn_weights = nn.Parameter(torch.randn(heads, heads))
-        self.reattn_norm = nn.Sequential(_Rearrange('b h i j -> b i j h'), nn.LayerNorm(heads), _Rearrange('b i j h -> b h i j'))
+        # the two permutes around the LayerNorm over heads are the re-attention kernels' indexing
+        self.reattn_norm = nn.Sequential(E.Rearrange('b h i j -> b i j h'), nn.LayerNorm(heads), E.Rearrange('b i j h -> b h i j'))
         self.to_out = nn.Sequential(nn.Linear(inner_dim, dim), nn.Dropout(dropout))
 
 
@@ -134,7 +95,7 @@ class LayerFn(torch.autograd.Function):
         K.bgemm((qkv, 0), sp, (qkv, inner), spT, (S, 0), mat, B, H, n, n, dh, scale)
         wrd, rgd, rbd = wr.detach(), rg.detach(), rb.detach()
         if robust:
-            P, lse, avec, bvec = K.sinkhorn_fwd(S, iters=SINKHORN_ITERS)
+            P, lse, avec, bvec = K.sinkhorn_fwd(S, iters=K.SINKHORN_ITERS)
             A = K.reattn_norm_fwd(P, wrd, rgd, rbd, epsr, a_dtype=torch.bfloat16)
             stats = (S, lse, avec, bvec)
         else:
@@ -179,7 +140,7 @@ class LayerFn(torch.autograd.Function):
             S, lse, avec, bvec = stats
             dP, dwr, drg, drb = K.reattn_norm_bwd(dA, P, wrd, rgd, epsr)
             del dA, P
-            dS = K.sinkhorn_bwd(S, dP, lse, avec, bvec, iters=SINKHORN_ITERS)
+            dS = K.sinkhorn_bwd(S, dP, lse, avec, bvec, iters=K.SINKHORN_ITERS)
             del dP, S
         else:
             dS, dwr, drg, drb = K.reattn_softmax_bwd(dA, P, wrd, rgd, epsr)
@@ -208,9 +169,7 @@ class Transformer(nn.Module):
             ]))
 
     def _check_forward(self, x) -> None:
-        E.require_cuda(x)
-        if E._RECORDING is not None:
-            raise NotImplementedError("attention-map recording is not implemented for DeepViT")
+        E.require_run(x, "DeepViT")
         if self.training and self.dropout > 0:
             raise NotImplementedError("dropout > 0 in training is not implemented for DeepViT (eval mode runs)")
         if x.dim() != 3:
@@ -250,7 +209,7 @@ class DeepViT(nn.Module):
         assert pool in {'cls', 'mean'}, 'pool type must be either cls (cls token) or mean (mean pooling)'
         self.patch_size, self.channels = patch_size, channels
         self.to_patch_embedding = nn.Sequential(
-            _Rearrange('b c (h p1) (w p2) -> b (h w) (p1 p2 c)', p1=patch_size, p2=patch_size), nn.Linear(patch_dim, dim))
+            E.Rearrange('b c (h p1) (w p2) -> b (h w) (p1 p2 c)', p1=patch_size, p2=patch_size), nn.Linear(patch_dim, dim))
         self.pos_embedding = nn.Parameter(torch.randn(1, num_patches + 1, dim))
         self.cls_token = nn.Parameter(torch.randn(1, 1, dim))
         self.dropout = nn.Dropout(emb_dropout)
@@ -260,9 +219,7 @@ class DeepViT(nn.Module):
         self.mlp_head = nn.Sequential(nn.LayerNorm(dim), nn.Linear(dim, num_classes))
 
     def _check_forward(self, img) -> None:
-        E.require_cuda(img)
-        if E._RECORDING is not None:
-            raise NotImplementedError("attention-map recording is not implemented for DeepViT")
+        E.require_run(img, "DeepViT")
         if self.training and (self.dropout.p > 0 or self.transformer.dropout > 0):
             raise NotImplementedError("dropout / emb_dropout > 0 in training is not implemented for DeepViT (eval mode runs)")
         p, c = self.patch_size, self.channels

@@ -24,6 +24,7 @@ from dataclasses import dataclass
 from typing import Callable, List, NamedTuple, Optional, Sequence
 
 import torch
+from torch import nn
 
 from . import kernels as K
 from ._lib import (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_Q8, EPI_BIAS_RESIDUAL, EPI_DGELU, EPI_DGELU_Q8, EPI_NONE, NrvError)
@@ -122,13 +123,64 @@ WEIGHTS = WeightCache()
 
 
 # ----------------------------------------------------------------------------------------------
-# host helpers shared by the model ports (Swin, LeViT, PatchConvNet, CaiT, T2T-ViT): a port imports them from here, never
-# from another port
+# host helpers shared by the model ports (Swin, LeViT, PatchConvNet, CaiT, T2T-ViT, RvT, PiT, DeepViT, CCT, Twins-SVT): a port
+# imports them from here, never from another port
 # ----------------------------------------------------------------------------------------------
 def require_cuda(x: Tensor) -> None:
     if not x.is_cuda:
         raise NrvError("noise_robust_vit_amd runs on the MI355X (HIP) device only: move the module and its input to 'cuda'.  "
                        "There is deliberately no CPU fallback on this path.")
+
+
+def refuse_recording(what: str) -> None:
+    if _RECORDING is not None:
+        raise NotImplementedError(f"attention-map recording is not implemented for {what}")
+
+
+def require_run(x: Tensor, what: str) -> None:
+    """The guard in front of a port's schedule: a device tensor, and no record_attention around the call."""
+    require_cuda(x)
+    refuse_recording(what)
+
+
+class Holder(nn.Module):
+    """A module that only carries the reference's parameter names; the layer it belongs to runs as one fused schedule."""
+
+    def forward(self, *args, **kwargs):
+        raise NotImplementedError(f"{type(self).__name__} holds parameters only: its layer runs as one fused HIP schedule, call the "
+                                  "Transformer (or the model) that owns it")
+
+
+class Residual(Holder):
+    def __init__(self, fn):
+        super().__init__()
+        self.fn = fn
+
+
+class PreNorm(Holder):
+    def __init__(self, dim, fn):
+        super().__init__()
+        self.norm = nn.LayerNorm(dim)
+        self.fn = fn
+
+
+class FeedForward(Holder):
+    def __init__(self, dim, hidden_dim, dropout=0.):
+        super().__init__()
+        if dim % 8 or hidden_dim % 8:
+            raise NotImplementedError(f"FeedForward {dim} -> {hidden_dim}: the kernels take multiples of 8")
+        self.net = nn.Sequential(nn.Linear(dim, hidden_dim), nn.GELU(), nn.Dropout(dropout), nn.Linear(hidden_dim, dim), nn.Dropout(dropout))
+
+
+class Rearrange(nn.Module):
+    """Placeholder for an einops Rearrange (no parameters): what the pattern names is the kernels' addressing."""
+
+    def __init__(self, pattern: str, **axes):
+        super().__init__()
+        self.pattern, self.axes = pattern, axes
+
+    def extra_repr(self):
+        return ", ".join([repr(self.pattern)] + [f"{k}={v}" for k, v in self.axes.items()])
 
 
 _INDEX_CACHE = {}
@@ -155,13 +207,49 @@ def scatter_bf16(src: Tensor, index: Tensor, rows: int) -> Tensor:
     return K.scatter_rows(src.view(torch.float32), index, rows).view(torch.bfloat16)
 
 
-def conv_images(w: Tensor, KP: int):
-    """bf16 images of a Conv2d weight [Co, C, ks, ks] in the unfold's (ky, kx, c) feature order, padded to KP columns."""
-    Co = w.shape[0]
-    w2 = w.detach().permute(0, 2, 3, 1).reshape(Co, -1)
+def conv_to_columns(w: Tensor, KP: int) -> Tensor:
+    """A Conv2d weight [Co, C, ks, ks] as [Co, KP] in the unfold's (ky, kx, c) feature order, zero columns behind ks * ks * C."""
+    w2 = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
     if w2.shape[1] != KP:
         w2 = torch.nn.functional.pad(w2, (0, KP - w2.shape[1]))
-    return K.cast_transpose(w2.contiguous(), need_t=True)
+    return w2.contiguous()
+
+
+def conv_from_columns(wc: Tensor, C: int, ks: int) -> Tensor:
+    """The inverse of conv_to_columns: [Co, KP] in (ky, kx, c) order -> [Co, C, ks, ks] (a weight gradient dy^T cols)."""
+    return wc[:, :ks * ks * C].reshape(wc.shape[0], ks, ks, C).permute(0, 3, 1, 2).contiguous()
+
+
+def conv_images(w: Tensor, KP: int):
+    """bf16 images (W, W^T) of a Conv2d weight in the unfold's feature order, padded to KP columns."""
+    return K.cast_transpose(conv_to_columns(w.detach(), KP), need_t=True)
+
+
+def conv_cols(src: Tensor, w: Tensor, B: int, C: int, H: int, W: int, ks: int, stride: int, pad: int, nhwc: bool):
+    """One layer of a conv stem as a GEMM: (im2col rows of src, bf16 W, bf16 W^T).  The images are staged on every call."""
+    cols = K.conv_unfold(src, B, C, H, W, ks, stride, pad, nhwc=nhwc)
+    return (cols, *conv_images(w, cols.shape[1]))
+
+
+def conv_wgrad(dy: Tensor, cols: Tensor, C: int, ks: int) -> Tensor:
+    """The layer's weight gradient dy^T cols in the parameter's [Co, C, ks, ks] order."""
+    return conv_from_columns(K.gemm_tn(dy, cols), C, ks)
+
+
+def conv_dx(dy: Tensor, wt: Tensor, B: int, C: int, H: int, W: int, ks: int, stride: int, pad: int) -> Tensor:
+    """The layer's input gradient dy W folded back to fp32 NHWC rows [B*H*W, C]."""
+    return K.conv_fold(K.gemm_nt(dy, wt, out_dtype=torch.bfloat16), B, C, H, W, ks, stride, pad)
+
+
+def padded_images(weight: Tensor, FP: int, need_t: bool):
+    """bf16 (W, W^T) of a projection [Co, ...] of F features whose GEMM rows carry FP >= F (a patch of 3 * 14 * 14 = 588 -> 592):
+    the unfold pads its rows with zero columns to the GEMM's K granularity, the projection gets matching ones.  FP == F comes
+    from the weight cache; the padded image is one small cast per call, outside it."""
+    F = weight[0].numel()
+    if FP == F:
+        return WEIGHTS.get(weight, need_t)
+    w2 = torch.nn.functional.pad(weight.detach().reshape(weight.shape[0], F).to(torch.float32), (0, FP - F))
+    return K.cast_transpose(w2, need_t=need_t)
 
 
 def linear(x16: Tensor, w: Tensor, b: Optional[Tensor], out_dtype=torch.bfloat16) -> Tensor:
@@ -442,13 +530,10 @@ def draw_keep(meta: BlockMeta, site: int, shape, device, p: Optional[float] = No
     return (torch.rand(shape, device=device) >= (meta.dropout if p is None else p)).to(torch.uint8)
 
 
-FUSED_DROP_DH = (32, 64, 80, 96, 128)          # nrv_attn_drop_fwd's head dims: those of nrv_attn_fwd (row-major)
-
-
 def attn_drop_fused(meta: BlockMeta, adrop) -> bool:
     """Whether the attention-weight dropout `adrop` of attn_half_fwd runs inside the fused kernels."""
     return (adrop is not None and meta.attn_dropout_fused and meta.mask_source is None and meta.attn_bias is None
-            and not meta.robust and meta.dim_head in FUSED_DROP_DH)
+            and not meta.robust and meta.dim_head in K.ATTN_FUSED_DH)
 
 
 def draw_attn_seeds(meta: BlockMeta, sites, device) -> List[Tensor]:
@@ -957,15 +1042,7 @@ class PatchEmbedFn(torch.autograd.Function):
         n = (H // patch) * (W // patch)
         D = weight.shape[0]
         patches = K.patch_unfold(img.detach(), patch, layout)
-        F, FP = C * patch * patch, patches.shape[1]
-        if FP == F:
-            wb, _ = WEIGHTS.get(weight, False)
-        else:
-            # patch sizes whose feature count is not a multiple of 8 (vit_h_14: 3 * 14 * 14 = 588): the unfold kernel pads the
-            # rows with zero columns to the GEMM's K granularity; the projection gets matching zero columns (one small cast
-            # per forward, outside the weight cache -- no BASELINE config takes this path)
-            w2 = torch.nn.functional.pad(weight.detach().reshape(weight.shape[0], -1).to(torch.float32), (0, FP - F))
-            wb, _ = K.cast_transpose(w2, need_t=False)
+        wb, _ = padded_images(weight, patches.shape[1], False)       # vit_h_14's 588 features; no BASELINE config is padded
         cls_slot = 0 if cls_token is None else 1
         S = n + cls_slot
         out = torch.empty(Bn * S, D, dtype=torch.float32, device=img.device)

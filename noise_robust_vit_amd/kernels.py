@@ -340,6 +340,9 @@ def colsum(X: Tensor, *, out: Optional[Tensor] = None, beta: float = 0.0) -> Ten
     return out
 
 
+ATTN_FUSED_DH = (32, 64, 80, 96, 128)    # nrv_attn_fwd's head dims (row-major qkv); nrv_attn_drop_fwd takes the same
+
+
 def attn_fwd(qkv: Tensor, B: int, N: int, H: int, dh: int, scale: float, layout: int = 0):
     """qkv bf16 [B*N, 3*H*dh] -> (out bf16 [B*N, H*dh], lse fp32 [B,H,N]).  simple_vit.py:68-75.
     `layout` (include/nrv.h NRV_ATTN_*_BLOCKED): qkv given as [3*H, B*N, dh] / out returned as [H, B*N, dh]."""
@@ -689,7 +692,7 @@ def attn_composed_bwd(qkv: Tensor, dout: Tensor, saved: ComposedSaved, B: int, N
 
 
 def _attn_sinkhorn_fwd_composed(qkv: Tensor, B: int, N: int, H: int, dh: int, scale: float, saved: Optional[dict] = None):
-    out, cs = attn_composed_fwd(qkv, B, N, H, dh, scale, iters=3)
+    out, cs = attn_composed_fwd(qkv, B, N, H, dh, scale, iters=SINKHORN_ITERS)
     # the model keeps ONE form of the saved statistics: [B,H,7,N] = a1 b1 a2 b2 a3 b3 a4 (cumulative), as the fused kernel writes it
     scal = torch.empty(B, H, 7, N, dtype=torch.float32, device=qkv.device)
     scal[:, :, 0::2] = cs.avec.reshape(B, H, 4, N)
@@ -704,7 +707,7 @@ def _attn_sinkhorn_bwd_composed(qkv: Tensor, dout: Tensor, lse: Tensor, scal: Te
     # P7 goes straight into the record (no local name here), so the backward frees it as soon as it is used
     cs = ComposedSaved(saved.pop("P7", None) if saved is not None else None, lse.reshape(B * H, N).contiguous(),
                        scal[:, :, 0::2].reshape(B * H, 4, N).contiguous(), scal[:, :, 1::2].reshape(B * H, 3, N).contiguous(),
-                       keep=None, pscale=1.0, iters=3, bias=None)
+                       keep=None, pscale=1.0, iters=SINKHORN_ITERS, bias=None)
     return attn_composed_bwd(qkv, dout, cs, B, N, H, dh, scale)
 
 
@@ -862,7 +865,10 @@ def adamw_flat(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, beta1: flo
          "nrv_adamw_f32")
 
 
-def sinkhorn_fwd(scores: Tensor, iters: int = 3):
+SINKHORN_ITERS = 3                       # SinkhornAttention's default (utils.py:1025-1037)
+
+
+def sinkhorn_fwd(scores: Tensor, iters: int = SINKHORN_ITERS):
     """SinkhornAttention(scores) on a materialised fp32 score tensor [..., R, C] (utils.py:1025-1037) -> (P, lse, avec, bvec)."""
     _f32(scores, "scores")
     if scores.dim() < 2:
@@ -881,7 +887,7 @@ def sinkhorn_fwd(scores: Tensor, iters: int = 3):
     return out, lse, avec, bvec
 
 
-def sinkhorn_bwd(scores: Tensor, dout: Tensor, lse: Tensor, avec: Tensor, bvec: Tensor, iters: int = 3) -> Tensor:
+def sinkhorn_bwd(scores: Tensor, dout: Tensor, lse: Tensor, avec: Tensor, bvec: Tensor, iters: int = SINKHORN_ITERS) -> Tensor:
     _f32(scores, "scores"); _f32(dout, "dout")
     s = scores.contiguous()
     d = dout.contiguous()

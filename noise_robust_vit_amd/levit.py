@@ -124,8 +124,7 @@ class StemFn(torch.autograd.Function):
         for li, cbn in enumerate(convs):
             c = cbn.c
             Cin, Co = c.in_channels, c.out_channels
-            cols = K.conv_unfold(src, B, Cin, H, W, 3, 2, 1, nhwc=li > 0)
-            wb, wt = E.conv_images(c.weight, cols.shape[1])
+            cols, wb, wt = E.conv_cols(src, c.weight, B, Cin, H, W, 3, 2, 1, li > 0)
             st = _BnState(cbn.bn, K.gemm_nt(cols, wb, out_dtype=torch.float32))
             Ho, Wo = K.conv_out_size(H, 3, 2, 1), K.conv_out_size(W, 3, 2, 1)
             layers.append((cols, wt, st, (Cin, H, W)))
@@ -147,13 +146,9 @@ class StemFn(torch.autograd.Function):
             cols, wt, st, (Cin, H, W) = layers[li]
             bn = convs[li].bn
             dy, dg, db = st.backward(dz, bn.weight, bn.bias, act=act)
-            dwi = K.gemm_tn(dy, cols)                                 # [Co, KP] in (ky, kx, c) order
-            w = convs[li].c.weight
-            Co, _, ks, _ = w.shape
-            grads[3 * li:3 * li + 3] = [dwi[:, :ks * ks * Cin].reshape(Co, ks, ks, Cin).permute(0, 3, 1, 2).contiguous(), dg, db]
+            grads[3 * li:3 * li + 3] = [E.conv_wgrad(dy, cols, Cin, 3), dg, db]
             if li > 0:
-                dcols = K.gemm_nt(dy, wt, out_dtype=torch.bfloat16)
-                dz, act = K.conv_fold(dcols, B, Cin, H, W, 3, 2, 1), True
+                dz, act = E.conv_dx(dy, wt, B, Cin, H, W, 3, 2, 1), True
         return (None, None, *grads)
 
 
@@ -567,9 +562,7 @@ class LeViT(nn.Module):
         return {x for x in self.state_dict().keys() if "attention_biases" in x}
 
     def forward(self, x: Tensor) -> Tensor:
-        E.require_cuda(x)
-        if E._RECORDING is not None:
-            raise NotImplementedError("attention-map recording is not implemented for LeViT")
+        E.require_run(x, "LeViT")
         B, _, Hi, Wi = x.shape
         r = Hi
         for _ in self._convs:

@@ -223,8 +223,7 @@ class StemFn(torch.autograd.Function):
         src, layers = img.detach().contiguous(), []
         for li, w in enumerate(weights):
             Co = w.shape[0]
-            cols = K.conv_unfold(src, B, Cin, H, W, 3, 2, 1, nhwc=li > 0)
-            wb, wt = E.conv_images(w, cols.shape[1])
+            cols, wb, wt = E.conv_cols(src, w, B, Cin, H, W, 3, 2, 1, li > 0)
             if li < len(weights) - 1:
                 gd = torch.empty(cols.shape[0], Co, dtype=torch.bfloat16, device=img.device)
                 src = K.gemm_nt(cols, wb, out_dtype=torch.bfloat16, epilogue=EPI_BIAS_GELU, bias=_zeros(Co, img.device), aux_out=gd)
@@ -233,7 +232,7 @@ class StemFn(torch.autograd.Function):
                 x32 = K.gemm_nt(cols, wb, out_dtype=torch.float32)
             layers.append((cols, wt, gd, (Cin, H, W)))
             Cin, H, W = Co, K.conv_out_size(H, 3, 2, 1), K.conv_out_size(W, 3, 2, 1)
-        ctx.layers, ctx.B, ctx.shapes = layers, B, [w.shape for w in weights]
+        ctx.layers, ctx.B = layers, B
         return x32
 
     @staticmethod
@@ -243,12 +242,9 @@ class StemFn(torch.autograd.Function):
         dy = K.cast_bf16(dx.to(torch.float32).contiguous())
         for li in range(len(layers) - 1, -1, -1):
             cols, wt, _, (Cin, H, W) = layers[li]
-            Co, _, ks, _ = ctx.shapes[li]
-            dwi = K.gemm_tn(dy, cols)                                   # [Co, KP] in (ky, kx, c) order
-            grads[li] = dwi[:, :ks * ks * Cin].reshape(Co, ks, ks, Cin).permute(0, 3, 1, 2).contiguous()
+            grads[li] = E.conv_wgrad(dy, cols, Cin, 3)
             if li > 0:
-                dcols = K.gemm_nt(dy, wt, out_dtype=torch.bfloat16)
-                dz = K.conv_fold(dcols, B, Cin, H, W, 3, 2, 1)
+                dz = E.conv_dx(dy, wt, B, Cin, H, W, 3, 2, 1)
                 dy = K.dgelu_rows(dz, layers[li - 1][2])              # the GELU that produced this conv's input
         return (None, *grads)
 
@@ -436,9 +432,7 @@ class PatchConvnet(nn.Module):
         self.head = nn.Linear(self.embed_dim, num_classes) if num_classes > 0 else nn.Identity()
 
     def _check_forward(self, x: Tensor) -> None:
-        E.require_cuda(x)
-        if E._RECORDING is not None:
-            raise NotImplementedError("attention-map recording is not implemented for PatchConvNet")
+        E.require_run(x, "PatchConvNet")
         if any(b.attn.robust for b in self.blocks_token_only):
             raise NotImplementedError(_ROBUST_MSG)
         if self.training and (self.drop_rate > 0 or self.attn_drop_rate > 0):

@@ -57,28 +57,10 @@ def conv_output_size(image_size, kernel_size, stride, padding=0):
 # ----------------------------------------------------------------------------------------------
 # modules (parameter holders with the reference's names and construction order)
 # ----------------------------------------------------------------------------------------------
-class _Holder(nn.Module):
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError(f"{type(self).__name__} holds parameters only: a PiT stage and a Pool run as one fused HIP schedule, "
-                                  "call the Transformer, the Pool (or PiT) that owns it")
+PreNorm, FeedForward = E.PreNorm, E.FeedForward
 
 
-class PreNorm(_Holder):
-    def __init__(self, dim, fn):
-        super().__init__()
-        self.norm = nn.LayerNorm(dim)
-        self.fn = fn
-
-
-class FeedForward(_Holder):
-    def __init__(self, dim, hidden_dim, dropout=0.):
-        super().__init__()
-        if dim % 8 or hidden_dim % 8:
-            raise NotImplementedError(f"FeedForward {dim} -> {hidden_dim}: the kernels take multiples of 8")
-        self.net = nn.Sequential(nn.Linear(dim, hidden_dim), nn.GELU(), nn.Dropout(dropout), nn.Linear(hidden_dim, dim), nn.Dropout(dropout))
-
-
-class Attention(_Holder):
+class Attention(E.Holder):
     def __init__(self, dim, heads=8, dim_head=64, dropout=0.):
         super().__init__()
         inner_dim = dim_head * heads
@@ -96,7 +78,7 @@ class Attention(_Holder):
         self.to_out = nn.Sequential(nn.Linear(inner_dim, dim), nn.Dropout(dropout))
 
 
-class DepthWiseConv2d(_Holder):
+class DepthWiseConv2d(E.Holder):
     def __init__(self, dim_in, dim_out, kernel_size, padding, stride, bias=True):
         super().__init__()
         if kernel_size != 3 or stride != 2 or padding != 1 or not bias or dim_out != 2 * dim_in:
@@ -108,9 +90,7 @@ class DepthWiseConv2d(_Holder):
 
 def _check_stream(x, what: str) -> int:
     """The side of the square token grid of x [B, 1 + g*g, dim]."""
-    E.require_cuda(x)
-    if E._RECORDING is not None:
-        raise NotImplementedError("attention-map recording is not implemented for PiT")
+    E.require_run(x, "PiT")
     g = isqrt(max(x.shape[1] - 1, 0)) if x.dim() == 3 else 0
     if x.dim() != 3 or g < 1 or x.shape[1] != 1 + g * g:
         raise NotImplementedError(f"{what} takes x [B, 1 + g*g, dim] on a square g x g token grid, got {tuple(x.shape)}")
@@ -220,12 +200,7 @@ class PatchEmbedFn(torch.autograd.Function):
         D, F = weight.shape
         cols = K.unfold_patches(img.detach().contiguous(), ks, stride)
         n, FP = cols.shape[0] // Bn, cols.shape[1]
-        if FP == F:
-            wb, _ = WEIGHTS.get(weight, False)
-        else:
-            # 3 * 14 * 14 = 588 features: the unfold pads the rows with zero columns to the GEMM's K granularity and the
-            # projection gets matching zero columns (one small cast per forward, outside the weight cache)
-            wb, _ = K.cast_transpose(torch.nn.functional.pad(weight.detach().to(torch.float32), (0, FP - F)), need_t=False)
+        wb, _ = E.padded_images(weight, FP, False)                         # 3 * 14 * 14 = 588 features ride as 592
         S = n + 1
         pos2 = pos.detach().reshape(-1, D).to(torch.float32)
         out = torch.empty(Bn * S, D, dtype=torch.float32, device=img.device)
@@ -249,14 +224,6 @@ class PatchEmbedFn(torch.autograd.Function):
         return None, dw.reshape(wshape), dsum[1:].sum(0), dsum.reshape(pos_shape), dsum[0].reshape(1, 1, D), None, None
 
 
-class _Rearrange(nn.Module):
-    """Placeholder for einops' Rearrange('b c n -> b n c') at to_patch_embedding.1 (no parameters; nrv_unfold_patches writes
-    token-major rows)."""
-
-    def extra_repr(self):
-        return "'b c n -> b n c'"
-
-
 class PiT(nn.Module):
     """pit.py:121-186 with the reference's constructor arguments, plus `robust` (see the module docstring)."""
 
@@ -276,7 +243,7 @@ class PiT(nn.Module):
         self.image_size = image_size
         self.patch_size = patch_size
         self.emb_dropout = emb_dropout
-        self.to_patch_embedding = nn.Sequential(nn.Unfold(kernel_size=patch_size, stride=patch_size // 2), _Rearrange(),
+        self.to_patch_embedding = nn.Sequential(nn.Unfold(kernel_size=patch_size, stride=patch_size // 2), E.Rearrange('b c n -> b n c'),
                                                 nn.Linear(patch_dim, dim))
         output_size = conv_output_size(image_size, patch_size, patch_size // 2)
         num_patches = output_size ** 2
@@ -300,8 +267,7 @@ class PiT(nn.Module):
         E.require_cuda(img)
         if self.training and (self.emb_dropout > 0 or any(getattr(m, "p", 0.) > 0 for m in self.layers)):
             raise NotImplementedError("dropout / emb_dropout > 0 in training is not implemented for PiT (eval mode runs)")
-        if E._RECORDING is not None:
-            raise NotImplementedError("attention-map recording is not implemented for PiT")
+        E.refuse_recording("PiT")
         p = self.patch_size
         if img.dim() != 4 or img.shape[2] != img.shape[3] or img.shape[2] < p:
             raise NotImplementedError(f"PiT takes square [B, C, S, S] images, got {tuple(img.shape)}")

@@ -48,7 +48,6 @@ Tensor = torch.Tensor
 __all__ = ["RvT", "Transformer", "Attention", "FeedForward", "GEGLU", "SpatialConv", "DepthWiseConv2d", "PreNorm",
            "AxialRotaryEmbedding", "rotate_every_two"]
 
-_FUSED_DH = (32, 64, 80, 96, 128)        # nrv_attn_fwd's head dims
 _LD_LIMIT = (1 << 31) // 1280            # the NT GEMM's epilogue addresses 320 fp32 rows of ldc with 32-bit byte offsets
 
 
@@ -99,13 +98,7 @@ class AxialRotaryEmbedding(nn.Module):
 # ----------------------------------------------------------------------------------------------
 # modules (parameter holders with the reference's names and construction order)
 # ----------------------------------------------------------------------------------------------
-class _Holder(nn.Module):
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError(f"{type(self).__name__} holds parameters only: an RvT layer runs as one fused HIP schedule, "
-                                  "call the Transformer (or RvT) that owns it")
-
-
-class DepthWiseConv2d(_Holder):
+class DepthWiseConv2d(E.Holder):
     def __init__(self, dim_in, dim_out, kernel_size, padding, stride=1, bias=True):
         super().__init__()
         if stride != 1 or bias or padding != kernel_size // 2 or kernel_size not in (3, 5, 7):
@@ -115,25 +108,21 @@ class DepthWiseConv2d(_Holder):
             nn.Conv2d(dim_in, dim_out, kernel_size=1, bias=bias))
 
 
-class PreNorm(_Holder):
-    def __init__(self, dim, fn):
-        super().__init__()
-        self.norm = nn.LayerNorm(dim)
-        self.fn = fn
+PreNorm = E.PreNorm
 
 
-class SpatialConv(_Holder):
+class SpatialConv(E.Holder):
     def __init__(self, dim_in, dim_out, kernel, bias=False):
         super().__init__()
         self.conv = DepthWiseConv2d(dim_in, dim_out, kernel, padding=kernel // 2, bias=False)
         self.cls_proj = nn.Linear(dim_in, dim_out) if dim_in != dim_out else nn.Identity()
 
 
-class GEGLU(_Holder):
+class GEGLU(E.Holder):
     pass
 
 
-class FeedForward(_Holder):
+class FeedForward(E.Holder):
     def __init__(self, dim, hidden_dim, dropout=0., use_glu=True):
         super().__init__()
         if dim % 8 or hidden_dim % 8:
@@ -143,7 +132,7 @@ class FeedForward(_Holder):
                                  nn.Dropout(dropout), nn.Linear(hidden_dim, dim), nn.Dropout(dropout))
 
 
-class Attention(_Holder):
+class Attention(E.Holder):
     def __init__(self, dim, heads=8, dim_head=64, dropout=0., use_rotary=True, use_ds_conv=True, conv_query_kernel=5):
         super().__init__()
         inner_dim = dim_head * heads
@@ -179,7 +168,7 @@ def _cls_rows(t: Tensor, B: int, N: int, cols: int) -> Tensor:
 def _attention_kind(dh: int, robust: bool) -> str:
     if robust:
         return "sinkhorn"
-    return "softmax" if dh in _FUSED_DH else "composed"
+    return "softmax" if dh in K.ATTN_FUSED_DH else "composed"
 
 
 class LayerFn(torch.autograd.Function):
@@ -322,9 +311,7 @@ class Transformer(nn.Module):
         return [(a.fn.to_q.weight, a.fn.to_kv.weight) for a, _ in self.layers if not a.fn.use_ds_conv]
 
     def _check(self, x, g: int) -> None:
-        E.require_cuda(x)
-        if E._RECORDING is not None:
-            raise NotImplementedError("attention-map recording is not implemented for RvT")
+        E.require_run(x, "RvT")
         if self.training and self.p > 0:
             raise NotImplementedError("dropout > 0 in training is not implemented for RvT (eval mode runs)")
         if x.dim() != 3 or x.shape[1] != 1 + g * g:
@@ -357,18 +344,6 @@ class Transformer(nn.Module):
         return self.run(x.to(torch.float32).contiguous().reshape(B * N, D), B, g).reshape(B, N, D)
 
 
-class _Rearrange(nn.Module):
-    """Placeholder for einops' Rearrange('b c (h p1) (w p2) -> b (h w) (p1 p2 c)') at to_patch_embedding.0 (no parameters; the
-    unfold runs in nrv_patch_unfold)."""
-
-    def __init__(self, patch_size: int):
-        super().__init__()
-        self.patch_size = patch_size
-
-    def extra_repr(self):
-        return f"'b c (h p1) (w p2) -> b (h w) (p1 p2 c)', p1={self.patch_size}, p2={self.patch_size}"
-
-
 class RvT(nn.Module):
     """rvt.py:178-211 with the reference's constructor arguments, plus `robust` (see the module docstring)."""
 
@@ -383,7 +358,8 @@ class RvT(nn.Module):
         patch_dim = channels * patch_size ** 2
         self.patch_size = patch_size
         self.emb_dropout = emb_dropout
-        self.to_patch_embedding = nn.Sequential(_Rearrange(patch_size), nn.Linear(patch_dim, dim))
+        self.to_patch_embedding = nn.Sequential(E.Rearrange('b c (h p1) (w p2) -> b (h w) (p1 p2 c)', p1=patch_size, p2=patch_size),
+                                                nn.Linear(patch_dim, dim))
         self.cls_token = nn.Parameter(torch.randn(1, 1, dim))
         self.transformer = Transformer(dim, depth, heads, dim_head, mlp_dim, image_size, dropout, use_rotary, use_ds_conv, use_glu,
                                        robust=robust)

@@ -332,8 +332,7 @@ class SwinTransformerBlock(nn.Module):
         if a.dropout > 0.0 or a.attention_dropout > 0.0:
             raise NotImplementedError("dropout > 0 / attention_dropout > 0 are not implemented: the reference applies them with "
                                       "F.dropout(..., training=True) (swin.py:248,251), i.e. even in eval mode")
-        if E._RECORDING is not None:
-            raise NotImplementedError("attention-map recording is not implemented for the Swin window attention")
+        E.refuse_recording("the Swin window attention")
 
     def run(self, x: Tensor, B: int, H: int, W: int) -> Tensor:
         """fp32 stream [B*H*W, C] -> the same shape."""

@@ -36,7 +36,6 @@ from .lucid_vit import Transformer
 
 MAX_KERNEL = 7
 MAX_STAGE_DIM = 4096
-_FUSED_DH = (32, 64, 80, 96, 128)        # nrv_attn_fwd's streaming head dims
 
 
 def exists(val):
@@ -80,7 +79,7 @@ def _padded_vec(b: torch.Tensor, n: int) -> torch.Tensor:
 def _attention_kind(cp: int) -> str:
     if K.attn_wide_shape(cp):
         return "wide"
-    return "fused" if cp in _FUSED_DH else "composed"
+    return "fused" if cp in K.ATTN_FUSED_DH else "composed"
 
 
 class _SplitFn(torch.autograd.Function):
@@ -213,8 +212,7 @@ class PatchEmbedding(nn.Sequential):
     """The reference's `to_patch_embedding` Sequential (t2t.py:58-91), run through the soft-split and stage kernels."""
 
     def forward(self, img):
-        if E._RECORDING is not None:
-            raise NotImplementedError("recording attention maps is not implemented for T2TViT")
+        E.refuse_recording("T2TViT")
         if img.dim() != 4 or img.shape[2] != img.shape[3]:
             raise NotImplementedError(f"T2TViT takes square [B, C, S, S] images, got {tuple(img.shape)}")
         mods = list(self)
@@ -312,8 +310,7 @@ class T2TViT(nn.Module):
     def forward(self, img):
         if self.training and (self.dropout.p > 0.0 or getattr(self.transformer, "p", 0.0) > 0.0):
             raise NotImplementedError("dropout / emb_dropout > 0 in training is not implemented for T2TViT")
-        if E._RECORDING is not None:
-            raise NotImplementedError("recording attention maps is not implemented for T2TViT")
+        E.refuse_recording("T2TViT")
         if img.dim() != 4 or img.shape[2] != img.shape[3]:
             raise NotImplementedError(f"T2TViT takes square [B, C, S, S] images, got {tuple(img.shape)}")
         x = self.to_patch_embedding(img)

@@ -70,19 +70,10 @@ def group_by_key_prefix_and_remove_prefix(prefix, d):
 # ----------------------------------------------------------------------------------------------
 # modules (parameter holders with the reference's names and construction order)
 # ----------------------------------------------------------------------------------------------
-class _Holder(nn.Module):
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError(f"{type(self).__name__} holds parameters only: a Twins-SVT stage runs as fused HIP schedules on "
-                                  "token-major rows, call the Transformer (or TwinsSVT) that owns it")
+Residual = E.Residual
 
 
-class Residual(_Holder):
-    def __init__(self, fn):
-        super().__init__()
-        self.fn = fn
-
-
-class LayerNorm(_Holder):
+class LayerNorm(E.Holder):
     def __init__(self, dim, eps=1e-5):
         super().__init__()
         self.eps = eps
@@ -90,7 +81,7 @@ class LayerNorm(_Holder):
         self.b = nn.Parameter(torch.zeros(1, dim, 1, 1))
 
 
-class PreNorm(_Holder):
+class PreNorm(E.Holder):
     def __init__(self, dim, fn):
         super().__init__()
         self.norm = LayerNorm(dim)
@@ -102,7 +93,7 @@ def _check_dim(dim: int, what: str) -> None:
         raise NotImplementedError(f"{what}: dim {dim} must be a multiple of 8 and at most 4096 (LayerNorm and the GEMMs)")
 
 
-class FeedForward(_Holder):
+class FeedForward(E.Holder):
     def __init__(self, dim, mult=4, dropout=0.):
         super().__init__()
         _check_dim(dim, "FeedForward")
@@ -110,7 +101,7 @@ class FeedForward(_Holder):
                                  nn.Dropout(dropout))
 
 
-class PatchEmbedding(_Holder):
+class PatchEmbedding(E.Holder):
     def __init__(self, *, dim, dim_out, patch_size):
         super().__init__()
         _check_dim(dim_out, "PatchEmbedding")
@@ -122,7 +113,7 @@ class PatchEmbedding(_Holder):
         self.proj = nn.Conv2d(patch_size ** 2 * dim, dim_out, 1)
 
 
-class PEG(_Holder):
+class PEG(E.Holder):
     def __init__(self, dim, kernel_size=3):
         super().__init__()
         if kernel_size not in (3, 5, 7):
@@ -138,7 +129,7 @@ def _check_heads(dim: int, heads: int, dim_head: int, what: str) -> None:
         raise NotImplementedError(f"{what}: heads {heads}")
 
 
-class LocalAttention(_Holder):
+class LocalAttention(E.Holder):
     def __init__(self, dim, heads=8, dim_head=64, dropout=0., patch_size=7, robust=False):
         super().__init__()
         _check_heads(dim, heads, dim_head, "LocalAttention")
@@ -155,7 +146,7 @@ class LocalAttention(_Holder):
         self.to_out = nn.Sequential(nn.Conv2d(inner_dim, dim, 1), nn.Dropout(dropout))
 
 
-class GlobalAttention(_Holder):
+class GlobalAttention(E.Holder):
     def __init__(self, dim, heads=8, dim_head=64, dropout=0., k=7, robust=False):
         super().__init__()
         _check_heads(dim, heads, dim_head, "GlobalAttention")
@@ -180,15 +171,6 @@ def _flat(p: Tensor) -> Tensor:
     return p.detach().reshape(-1)
 
 
-def _padded_images(weight: Tensor, FP: int):
-    """bf16 (W, W^T) of a [Co, F, 1, 1] weight whose GEMM rows carry FP >= F features (zero pad columns)."""
-    F = weight[0].numel()
-    if FP == F:
-        return WEIGHTS.get(weight, True)
-    w2 = torch.nn.functional.pad(weight.detach().reshape(weight.shape[0], F).to(torch.float32), (0, FP - F))
-    return K.cast_transpose(w2, need_t=True)
-
-
 class PatchEmbedFn(torch.autograd.Function):
     """PatchEmbedding (twins_svt.py:68-79): src is the NCHW image (stage 1, no gradient) or the fp32 stream [B*G*G, C];
     -> fp32 [B*g*g, dim_out], g = G / p."""
@@ -197,7 +179,7 @@ class PatchEmbedFn(torch.autograd.Function):
     def forward(ctx, src, weight, bias, B: int, C: int, G: int, p: int, rows: bool):
         s = K.cast_bf16(src.detach().to(torch.float32).contiguous()) if rows else src.detach().contiguous()
         cols = K.soft_split_fwd(s, B, C, G, G, p, p, 0, rows)
-        wb, _ = _padded_images(weight, cols.shape[1])
+        wb, _ = E.padded_images(weight, cols.shape[1], True)
         out = K.gemm_nt(cols, wb, out_dtype=torch.float32, epilogue=EPI_BIAS, bias=bias.detach())
         ctx.saved = cols
         ctx.cfg = (B, C, G, p, rows)
@@ -217,7 +199,7 @@ class PatchEmbedFn(torch.autograd.Function):
             dw = dw[:, :F].contiguous()                                       # the zero-padded feature columns are dropped
         dx = None
         if rows:
-            _, wt = _padded_images(weight, cols.shape[1])
+            _, wt = E.padded_images(weight, cols.shape[1], True)
             dcols = K.gemm_nt(d16, wt, out_dtype=torch.bfloat16)
             dx = K.soft_split_bwd(dcols, B, C, G, G, p, p, 0, ld=C)
         return dx, dw.reshape(weight.shape), db, None, None, None, None, None
@@ -403,12 +385,6 @@ class GlobalAttnFn(torch.autograd.Function):
 # ----------------------------------------------------------------------------------------------
 # the runnable modules
 # ----------------------------------------------------------------------------------------------
-def _check_run(x: Tensor, what: str) -> None:
-    E.require_cuda(x)
-    if E._RECORDING is not None:
-        raise NotImplementedError(f"attention-map recording is not implemented for {what}")
-
-
 class Transformer(nn.Module):
     """twins_svt.py:156-173.  forward(x [B, dim, g, g]) on the HIP device; `run` takes the fp32 token-major rows."""
 
@@ -427,7 +403,7 @@ class Transformer(nn.Module):
                 Residual(PreNorm(dim, FeedForward(dim, mlp_mult, dropout=dropout)))]))
 
     def _check(self, x: Tensor, g: int) -> None:
-        _check_run(x, "Twins-SVT")
+        E.require_run(x, "Twins-SVT")
         if self.training and self.p > 0:
             raise NotImplementedError("dropout > 0 in training is not implemented for Twins-SVT (eval mode runs)")
         for la, _, ga, _ in self.layers:
@@ -463,13 +439,6 @@ class Transformer(nn.Module):
         B, C, g, _ = x.shape
         rows = x.to(torch.float32).permute(0, 2, 3, 1).reshape(B * g * g, C)
         return self.run(rows, B, g).reshape(B, g, g, C).permute(0, 3, 1, 2)
-
-
-class _Rearrange(nn.Module):
-    """Placeholder for einops' Rearrange('... () () -> ...') behind the pooling (no parameters; the mean runs on token rows)."""
-
-    def extra_repr(self):
-        return "'... () () -> ...'"
 
 
 class TwinsSVT(nn.Module):
@@ -530,7 +499,7 @@ class TwinsSVT(nn.Module):
         self.layers = nn.Sequential(
             *layers,
             nn.AdaptiveAvgPool2d(1),
-            _Rearrange(),
+            E.Rearrange('... () () -> ...'),
             nn.Linear(dim, num_classes)
         )
 
@@ -538,7 +507,7 @@ class TwinsSVT(nn.Module):
         return []
 
     def forward(self, x):
-        _check_run(x, "Twins-SVT")
+        E.require_run(x, "Twins-SVT")
         if self.training and self.dropout_p > 0:
             raise NotImplementedError("dropout > 0 in training is not implemented for Twins-SVT (eval mode runs)")
         if x.dim() != 4 or x.shape[2] != x.shape[3]:

@@ -139,9 +139,10 @@ def test_product_never_imports_the_oracle_or_reads_the_reference():
 
 
 def test_no_model_port_imports_another_model_port():
-    """Swin, LeViT, PatchConvNet, CaiT and T2T-ViT share host helpers through encoder.py only, so that an edit to one port
-    cannot break another.  t2t.py builds on lucid_vit.Transformer, as the reference's T2T builds on its ViT."""
-    ports = {"swin", "levit", "patch_convnet", "cait", "t2t"}
+    """The ten model ports share host helpers through encoder.py only, so that an edit to one port cannot break another.
+    Two exceptions, neither of them a port: t2t.py builds on lucid_vit.Transformer, as the reference's T2T builds on its ViT,
+    and rvt.py on lucid_vit.Attention's fused [to_q; to_kv] projection."""
+    ports = {"swin", "levit", "patch_convnet", "cait", "t2t", "rvt", "pit", "deepvit", "cct", "twins_svt"}
     found = {p: _imports(os.path.join(ROOT, "noise_robust_vit_amd", p + ".py"), package="noise_robust_vit_amd") for p in ports}
     assert all("encoder" in f for f in found.values())                     # relative imports are seen at all
     crossing = {p: sorted(f & (ports - {p})) for p, f in found.items() if f & (ports - {p})}

@@ -177,6 +177,55 @@ typedef struct nrv_tn_plan { int tiles, splits, kt_q, kt_r, phased, direct, redu
 int nrv_gemm_nt_plan(int64_t M, int64_t N, int64_t K, int epilogue, int remap, nrv_nt_plan* plan);
 int nrv_gemm_tn_plan(int64_t M, int64_t N, int64_t T, int a_group, float beta, int dbias, nrv_tn_plan* plan);
 
+/* ------------------------------------------------------------------------------------------
+ * The split-K reduction as a side job of the NT launch that follows (added without an ABI bump: the ABI stays 19 and every
+ * prototype, plan answer and workspace size above is unchanged).
+ *
+ * A weight-gradient launch leaves fp32 slabs (and bias column sums) that a small, latency-bound reduction kernel adds up.  The
+ * persistent NT kernel lets the workgroups that have one tile fewer than the busiest ones start late; with a job attached they
+ * reduce equal contiguous shares of the slabs first, in place of (part of) that wait.  No workgroup waits for another: stream
+ * order guarantees that the slabs are complete.  The arithmetic and its order are those of the reduction kernel, so C and dbias
+ * are bit-identical whichever way a job is run.
+ *   nrv_gemm_tn_bf16_deferred: nrv_gemm_tn_bf16 without the reduction launch.  Same checks, plan and kernel; fills *job, whose
+ *     `pending` is 1 when slabs or a bias gradient remain to be reduced (0: a direct plan without dbias, C is complete).  The
+ *     workspace, C and dbias must stay valid until the job has run.  nrv_gemm_tn_bf16 is this call followed by nrv_splitk_reduce.
+ *   nrv_splitk_reduce: the stand-alone reduction of a job (nothing when pending == 0).
+ *   nrv_gemm_nt_bf16_side: nrv_gemm_nt_bf16 that also completes `job` on the same stream.  When the admission rule holds the
+ *     GEMM launch carries the job (*fused = 1); otherwise nrv_splitk_reduce runs first and the plain GEMM after it (*fused = 0).
+ *     The GEMM's operands must not alias the job's C, dbias or workspace.
+ *   nrv_gemm_nt_side_plan: read-only like nrv_gemm_nt_plan (no GPU needed).  `job_bytes`: the slab bytes of the job
+ *     (splits * M * N * 4; 0 for a job of bias sums only).
+ *     late        : workgroups that would take shares = grid - tiles % grid; 0 on the plain kernel, with a row remap, with
+ *                   tiles <= grid and with tiles % grid == 0;
+ *     share_bytes : slab bytes per share, ceil(job_bytes / late) (0 when late == 0);
+ *     admitted    : late > 0 and share_bytes <= B * (K / 64) * tile_m / 256, B the library's measured bytes per K-step.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct nrv_reduce_job {
+    const float* slabs; int64_t slab_stride;   /* [splits] slabs of M x N fp32 (NULL: a direct plan), elements between slabs */
+    float* C; int64_t ldc;                      /* C = beta * C + sum of the slabs */
+    const float* bias_ws; float* dbias;         /* [splits][M] column sums (NULL: no bias gradient) -> dbias */
+    int64_t M, N;
+    int splits;
+    float beta, dbias_beta;
+    int pending;
+} nrv_reduce_job;
+typedef struct nrv_nt_side_plan { int late, admitted; int64_t share_bytes; } nrv_nt_side_plan;
+int nrv_gemm_tn_bf16_deferred(const void* A, int64_t lda, const void* B, int64_t ldb,
+                              float* C, int64_t ldc, int64_t M, int64_t N, int64_t T, float beta,
+                              int64_t a_group, int64_t a_group_stride, int64_t a_row_offset,
+                              float* dbias, float dbias_beta,
+                              void* workspace, size_t workspace_bytes, nrv_reduce_job* job, void* stream);
+int nrv_splitk_reduce(const nrv_reduce_job* job, void* stream);
+int nrv_gemm_nt_bf16_side(const void* A, int64_t lda, const void* B, int64_t ldb,
+                          void* C, int c_dtype, int64_t ldc,
+                          int64_t M, int64_t N, int64_t K,
+                          int epilogue, const float* bias,
+                          const void* aux, int aux_dtype, int64_t ld_aux, int64_t aux_row_mod,
+                          void* aux_out, int64_t ld_aux_out,
+                          int64_t out_group, int64_t out_group_stride, int64_t out_row_offset,
+                          const nrv_reduce_job* job, int* fused, void* stream);
+int nrv_gemm_nt_side_plan(int64_t M, int64_t N, int64_t K, int epilogue, int remap, int64_t job_bytes, nrv_nt_side_plan* plan);
+
 /* Column sum (bias gradient of nn.Linear's backward): out[n] = beta*out[n] + sum_t X[t,n].
  *   X bf16 [T,N] ld; N % 8 == 0.  workspace: nrv_colsum_workspace(T, N) bytes. */
 size_t nrv_colsum_workspace(int64_t T, int64_t N);

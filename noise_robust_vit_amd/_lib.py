@@ -40,6 +40,18 @@ class TnPlan(ctypes.Structure):
     _fields_ = [("tiles", c_int), ("splits", c_int), ("kt_q", c_int), ("kt_r", c_int), ("phased", c_int), ("direct", c_int),
                 ("reduce", c_int)]
 
+class ReduceJob(ctypes.Structure):
+    """include/nrv.h `nrv_reduce_job`: the reduction a deferred weight-gradient launch leaves behind."""
+    _fields_ = [("slabs", c_void_p), ("slab_stride", c_int64), ("C", c_void_p), ("ldc", c_int64),
+                ("bias_ws", c_void_p), ("dbias", c_void_p), ("M", c_int64), ("N", c_int64),
+                ("splits", c_int), ("beta", c_float), ("dbias_beta", c_float), ("pending", c_int)]
+
+
+class NtSidePlan(ctypes.Structure):
+    """include/nrv.h `nrv_nt_side_plan`: the shares a side job would be cut into, and whether nrv_gemm_nt_bf16_side takes it."""
+    _fields_ = [("late", c_int), ("admitted", c_int), ("share_bytes", c_int64)]
+
+
 class BgemmPlan(ctypes.Structure):
     """include/nrv.h `nrv_bgemm_plan_t`: what nrv_bgemm would launch."""
     _fields_ = [("a_vec", c_int), ("b_vec", c_int), ("c_vec", c_int), ("tiles_m", c_int), ("tiles_n", c_int),
@@ -71,6 +83,15 @@ SIGNATURES = {
     "nrv_gemm_tn_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                  c_int64, c_int64, c_int64, c_float, c_int64, c_int64, c_int64,
                                  c_void_p, c_float, c_void_p, c_size_t, c_void_p]),
+    "nrv_gemm_tn_bf16_deferred": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                          c_int64, c_int64, c_int64, c_float, c_int64, c_int64, c_int64,
+                                          c_void_p, c_float, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "nrv_splitk_reduce": (c_int, [c_void_p, c_void_p]),
+    "nrv_gemm_nt_bf16_side": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int64,
+                                      c_int64, c_int64, c_int64, c_int, c_void_p,
+                                      c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64,
+                                      c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "nrv_gemm_nt_side_plan": (c_int, [c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_void_p]),
     "nrv_gemm_tn_grouped_workspace": (c_size_t, [c_void_p, c_int, c_int64]),
     "nrv_gemm_tn_grouped_bf16": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_size_t, c_void_p]),
     "nrv_colsum_workspace": (c_size_t, [c_int64, c_int64]),

@@ -69,6 +69,19 @@ struct EpiParams {
     int out_group, out_group_stride, out_row_offset;
 };
 
+// The reduction of one split-K launch: C = beta * C + sum_s slab[s], dbias = dbias_beta * dbias + sum_s bias_ws[s].  All values are
+// wave-uniform.  slabs == nullptr: a direct plan (only the bias sums), bias_ws == nullptr: no bias gradient; both: no job.
+struct ReduceJob {
+    const float* slabs;
+    long long slab_stride;
+    float* C;
+    long long ldc;
+    const float* bias_ws;
+    float* dbias;
+    int splits, M, N;
+    float beta, dbias_beta;
+};
+
 struct GemmNTParams {
     const bf16_t* A;
     const bf16_t* B;
@@ -78,6 +91,8 @@ struct GemmNTParams {
     int gn;                       // column-group width of the tile order (0 = plain row-major sweep)
     int ntiles;                   // gemm_nt8_kernel (persistent): tiles of the whole output, >= gridDim.x
     EpiParams e;
+    ReduceJob job;                // gemm_nt8_kernel: the side job of its late-starting workgroups (the previous split-K launch's reduction)
+    unsigned job_cycles_per_kib;  // ... and what a KiB of its slabs is taken to cost, in shader cycles (shortens the late start's naps)
 };
 
 struct GemmTNParams {
@@ -643,6 +658,141 @@ constexpr bool nt8_patches_behind() { return 2 * nt8_stage_bytes<C>() + 8 * 4096
 template <typename C>
 constexpr int nt8_lds_bytes() { return 2 * nt8_stage_bytes<C>() + (nt8_patches_behind<C>() ? 8 : 4) * 4096; }
 
+// Bias rows i = first + t, first + t + nthreads, ... < last: the `splits` column sums are loaded in groups of four ahead of the adds
+// (independent loads instead of a chain of `splits` dependent ones: 28 for dWo of ViT-B/16); the adds stay in split order.
+__device__ __forceinline__ void reduce_bias_rows(const ReduceJob& j, int first, int last, int t, int nthreads) {
+    for (int i = first + t; i < last; i += nthreads) {
+        const float* src = j.bias_ws + i;
+        float s = 0.f;
+        int k = 0;
+        for (; k + 4 <= j.splits; k += 4) {
+            const float b0 = src[(long long)k * j.M], b1 = src[(long long)(k + 1) * j.M];
+            const float b2 = src[(long long)(k + 2) * j.M], b3 = src[(long long)(k + 3) * j.M];
+            s += b0; s += b1; s += b2; s += b3;
+        }
+        for (; k < j.splits; ++k) s += src[(long long)k * j.M];
+        j.dbias[i] = j.dbias_beta != 0.f ? j.dbias_beta * j.dbias[i] + s : s;
+    }
+}
+
+// The 16-byte chunks [first, last) of C (chunk i = row i / (N / 4), columns 4 (i % (N / 4)) ..), 64 per step and four-wave group:
+// group `gid` of GROUPS takes the chunks first + 64 gid + lane of every step of 64 GROUPS.  Wave g of the group sums the slabs
+// s = g, g + 4, ... (4 independent loads in flight per lane), the four partial sums meet in the group's LDS patch and are added in
+// the fixed order ((p0 + p1) + (p2 + p3)): deterministic, and 4 x the loads in flight of one thread per chunk (the slabs of a ViT-S
+// weight gradient are 25-85 x 0.6-2.4 MB: latency-bound, not bandwidth-bound).  Every thread of the workgroup runs the same
+// number of steps (the barriers are the workgroup's); `part` is [GROUPS][4][64].
+template <int GROUPS>
+__device__ __forceinline__ void reduce_chunks(const ReduceJob& j, long long first, long long last, int gid, int g, int lane,
+                                              f32x4_t (*part)[4][64]) {
+    const long long n4 = j.N >> 2;
+    for (long long base = first; base < last; base += 64 * GROUPS) {             // workgroup-uniform
+        const long long i = base + gid * 64 + lane;
+        const bool ok = i < last;
+        const long long m = ok ? i / n4 : 0, c = ok ? (i - m * n4) * 4 : 0;
+        const float* src = j.slabs + m * j.N + c;
+        f32x4_t s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
+        if (ok) {
+            int k = g;
+            for (; k + 12 < j.splits; k += 16) {
+                s0 += __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(src + (long long)k * j.slab_stride));
+                s1 += __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(src + (long long)(k + 4) * j.slab_stride));
+                s2 += __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(src + (long long)(k + 8) * j.slab_stride));
+                s3 += __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(src + (long long)(k + 12) * j.slab_stride));
+            }
+            for (; k < j.splits; k += 4) s0 += __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(src + (long long)k * j.slab_stride));
+        }
+        part[gid][g][lane] = (s0 + s1) + (s2 + s3);
+        __syncthreads();
+        if (g == 0 && ok) {
+            f32x4_t s = (part[gid][0][lane] + part[gid][1][lane]) + (part[gid][2][lane] + part[gid][3][lane]);
+            float* dst = j.C + m * j.ldc + c;
+            if (j.beta != 0.f) s += *reinterpret_cast<const f32x4_t*>(dst) * j.beta;
+            __builtin_nontemporal_store(s, reinterpret_cast<f32x4_t*>(dst));      // the gradient buffer is next read by the clip norm, after the whole backward
+        }
+        __syncthreads();
+    }
+}
+
+// reduce_chunks for splits <= 12 inside a workgroup that has a CU to itself (the side job below): there the first loop above never
+// runs (g + 12 < splits is false for every wave), so s1 = s2 = s3 = 0 and a chunk needs ONE accumulator.  A four-wave group takes U
+// steps of 64 chunks at a time and a lane keeps U loads in flight per slab round instead of one: with eight waves on the CU and
+// nothing else to hide the latency behind, one load per lane reduced 7 GB/s per CU (profiles/r19_nt_side_reduce.txt).  The value
+// of every chunk is the same expression in the same order, (((0 + slab[g]) + slab[g + 4]) + slab[g + 8] + 0) + (0 + 0) per wave and
+// ((p0 + p1) + (p2 + p3)) across the waves: the same bits.  `part` is [GROUPS][U][4][64]; wave g finishes the steps g and g + 4.
+template <int GROUPS, int U>
+__device__ __forceinline__ void reduce_chunks_few(const ReduceJob& j, long long first, long long last, int gid, int g, int lane,
+                                                  f32x4_t (*part)[U][4][64]) {
+    const long long n4 = j.N >> 2;
+    const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
+    for (long long base = first; base < last; base += 64 * GROUPS * U) {          // workgroup-uniform
+        const long long i0 = base + (long long)gid * (64 * U) + lane;             // step u: chunk i0 + 64 u
+        const float* src[U];
+        f32x4_t s[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long i = i0 + 64 * u;
+            const bool ok = i < last;
+            const long long m = ok ? i / n4 : 0, c = ok ? (i - m * n4) * 4 : 0;   // a chunk behind the range reads chunk 0 (and is dropped)
+            src[u] = j.slabs + m * j.N + c;
+            s[u] = z;
+        }
+        for (int k = g; k < j.splits; k += 4) {
+            f32x4_t v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(src[u] + (long long)k * j.slab_stride));
+#pragma unroll
+            for (int u = 0; u < U; ++u) s[u] += v[u];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) part[gid][u][g][lane] = (s[u] + z) + (z + z);
+        __syncthreads();
+#pragma unroll
+        for (int u0 = 0; u0 < U; u0 += 4) {
+            const int u = u0 + g;
+            const long long i = i0 + 64 * u;
+            if (i < last) {
+                const long long m = i / n4, c = (i - m * n4) * 4;
+                f32x4_t t = (part[gid][u][0][lane] + part[gid][u][1][lane]) + (part[gid][u][2][lane] + part[gid][u][3][lane]);
+                float* dst = j.C + m * j.ldc + c;
+                if (j.beta != 0.f) t += *reinterpret_cast<const f32x4_t*>(dst) * j.beta;
+                __builtin_nontemporal_store(t, reinterpret_cast<f32x4_t*>(dst));
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// The side job of a late-starting workgroup of gemm_nt8_kernel: share `share` of `shares` equal contiguous shares of the job's chunks
+// and of its bias rows, the eight waves as two four-wave groups, the LDS patch (up to 64 KiB) at `smem` (the stage area, >= 96 KiB, unused before the
+// prologue).  No workgroup waits for another: the slabs are complete by stream order.  Returns the naps left of `naps` after what
+// the share is taken to have cost (an estimate from its bytes: product code reads no clock).  Ends with every load and store of the
+// workgroup drained and a barrier behind the last LDS use.
+__device__ __forceinline__ unsigned nt8_side_job(const ReduceJob& j, unsigned cycles_per_kib, unsigned share, unsigned shares,
+                                                 unsigned naps, char* smem) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (j.bias_ws != nullptr) {
+        const long long per = ((long long)j.M + shares - 1) / shares;
+        const long long f = (long long)share * per;
+        const int first = (int)(f < j.M ? f : j.M), last = (int)(f + per < j.M ? f + per : j.M);
+        reduce_bias_rows(j, first, last, tid, 512);
+    }
+    unsigned spent = 0;
+    if (j.slabs != nullptr) {
+        const long long total = (long long)j.M * (j.N >> 2);
+        const long long per = (total + shares - 1) / shares;
+        const long long f = (long long)share * per;
+        const long long first = f < total ? f : total, last = f + per < total ? f + per : total;
+        if (j.splits <= 12) reduce_chunks_few<2, 8>(j, first, last, wave >> 2, wave & 3, lane, reinterpret_cast<f32x4_t(*)[8][4][64]>(smem));   // 64 KiB
+        else reduce_chunks<2>(j, first, last, wave >> 2, wave & 3, lane, reinterpret_cast<f32x4_t(*)[4][64]>(smem));
+        const unsigned kib = (unsigned)(((last - first) * j.splits) >> 6);        // 16-byte chunks of every slab
+        spent = (unsigned)(((unsigned long long)kib * cycles_per_kib) / 8128u);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    return naps > spent ? naps - spent : 0u;
+}
+
 struct Nt8Tile {                     // what the staging ops and the epilogue of one output tile need (scalar registers)
     __amdgpu_buffer_rsrc_t ra0, ra1, rb0, rb1;
     unsigned ka1, kb1;
@@ -810,7 +960,11 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_nt8_kernel(const GemmNTPar
         if (ntiles > gridDim.x && rem != 0 && blockIdx.x >= rem) {
             const unsigned tile_cycles = (unsigned)nk * (C::MI * 330u) + 6000u;
             const unsigned span = tile_cycles - tile_cycles / 4;
-            const unsigned naps = (blockIdx.x - rem) * (span / 8128u) / (gridDim.x - rem);  // s_sleep 127 = 8128 cycles
+            unsigned naps = (blockIdx.x - rem) * (span / 8128u) / (gridDim.x - rem);        // s_sleep 127 = 8128 cycles
+            // Side job: the reduction of the split-K launch in front of this one, instead of (part of) the naps: these workgroups
+            // have a tile time to spare, and the reduction as a launch of its own is latency-bound and hides behind nothing.
+            if (p.job.slabs != nullptr || p.job.bias_ws != nullptr)
+                naps = nt8_side_job(p.job, p.job_cycles_per_kib, blockIdx.x - rem, gridDim.x - rem, naps, smem);
             for (unsigned i = 0; i < naps; ++i) __builtin_amdgcn_s_sleep(127);
         }
     }
@@ -1667,51 +1821,18 @@ __global__ __launch_bounds__(256) void tng_fixup_kernel(const GemmTNGParams p) {
     }
 }
 
-// C = beta * C + sum_s slab[s].  A block of 4 waves owns 64 consecutive 16-byte chunks of C; wave g sums the slabs
-// s = g, g + 4, ... (4 independent loads in flight per lane), the four partial sums meet in LDS and are added in the fixed
-// order ((p0 + p1) + (p2 + p3)): deterministic, and 4 x the loads in flight of one thread per chunk (the slabs of a ViT-S
-// weight gradient are 25-85 x 0.6-2.4 MB: the kernel is latency-bound, not bandwidth-bound).
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ slabs, long long slab_stride, int splits,
-                                                            float* __restrict__ C, long long ldc, int M, int N, float beta,
-                                                            const float* __restrict__ bias_ws, float* __restrict__ dbias, float dbias_beta) {
-    __shared__ f32x4_t part[4][64];
-    if (bias_ws != nullptr) {
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += gridDim.x * blockDim.x) {
-            float s = 0.f;
-            for (int k = 0; k < splits; ++k) s += bias_ws[(long long)k * M + i];
-            dbias[i] = dbias_beta != 0.f ? dbias_beta * dbias[i] + s : s;
-        }
+// The stand-alone reduction: a block of 4 waves owns 64 consecutive chunks of C per grid-stride step and 256 bias rows.
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(const ReduceJob j) {
+    __shared__ f32x4_t part[1][4][64];
+    if (j.bias_ws != nullptr) {
+        for (int r = blockIdx.x * 256; r < j.M; r += gridDim.x * 256)
+            reduce_bias_rows(j, r, r + 256 < j.M ? r + 256 : j.M, threadIdx.x, 256);
     }
-    if (slabs == nullptr) return;
+    if (j.slabs == nullptr) return;
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const long long n4 = N >> 2;
-    const long long total = (long long)M * n4;
-    for (long long base = (long long)blockIdx.x * 64; base < total; base += (long long)gridDim.x * 64) {     // block-uniform
-        const long long i = base + lane;
-        const bool ok = i < total;
-        const long long m = ok ? i / n4 : 0, c = ok ? (i - m * n4) * 4 : 0;
-        const float* src = slabs + m * N + c;
-        f32x4_t s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
-        if (ok) {
-            int k = g;
-            for (; k + 12 < splits; k += 16) {
-                s0 += __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(src + (long long)k * slab_stride));
-                s1 += __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(src + (long long)(k + 4) * slab_stride));
-                s2 += __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(src + (long long)(k + 8) * slab_stride));
-                s3 += __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(src + (long long)(k + 12) * slab_stride));
-            }
-            for (; k < splits; k += 4) s0 += __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(src + (long long)k * slab_stride));
-        }
-        part[g][lane] = (s0 + s1) + (s2 + s3);
-        __syncthreads();
-        if (g == 0 && ok) {
-            f32x4_t s = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
-            float* dst = C + m * ldc + c;
-            if (beta != 0.f) s += *reinterpret_cast<const f32x4_t*>(dst) * beta;
-            __builtin_nontemporal_store(s, reinterpret_cast<f32x4_t*>(dst));      // the gradient buffer is next read by the clip norm, after the whole backward
-        }
-        __syncthreads();
-    }
+    const long long total = (long long)j.M * (j.N >> 2);
+    for (long long base = (long long)blockIdx.x * 64; base < total; base += (long long)gridDim.x * 64)       // block-uniform
+        reduce_chunks<1>(j, base, base + 64 < total ? base + 64 : total, 0, g, lane, part);
 }
 
 template <typename KernelT>
@@ -1721,6 +1842,10 @@ int set_lds(KernelT k, int bytes) {
 
 // The launch plan of one NT GEMM: which tile configuration, which kernel, how many tiles and workgroups.  nt_plan() below is the ONLY
 // place that decides; the launch (launch_nt) and the read-only query (nrv_gemm_nt_plan) both go through it.
+// Side job of the persistent NT kernel (nt8_side_job): slab bytes a late-starting workgroup is taken to reduce per K-step time of a
+// 256-row tile (8 x 330 cycles), with the other CUs in their K loops.  It sets the admission rule (nt_side_plan) and the nap estimate.
+constexpr unsigned NT_SIDE_BYTES_PER_KSTEP = 40 * 1024;       // measured: jobs that need <= 36.4 KiB gain, from 45.3 KiB on they lose (profiles/r19_nt_side_reduce.txt)
+
 struct NtPlan {
     int tile;               // 256 / 320 / 192 / 128 rows of a 256-column tile, or 1384 = the 384 x 128 tile
     int tbm, tbn;           // tile rows, tile columns
@@ -1874,14 +1999,16 @@ TnPlan tn_plan(int64_t M, int64_t N, int64_t T, bool a_group = false, float beta
 
 }  // namespace
 
-extern "C" int nrv_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int64_t ldb,
-                                void* C, int c_dtype, int64_t ldc,
-                                int64_t M, int64_t N, int64_t K,
-                                int epilogue_id, const float* bias,
-                                const void* aux, int aux_dtype, int64_t ld_aux, int64_t aux_row_mod,
-                                void* aux_out, int64_t ld_aux_out,
-                                int64_t out_group, int64_t out_group_stride, int64_t out_row_offset,
-                                void* stream) {
+namespace {
+// nrv_gemm_nt_bf16 and nrv_gemm_nt_bf16_side: the argument checks and the launch; `job` (optional) rides on the launch
+int gemm_nt_launch(const void* A, int64_t lda, const void* B, int64_t ldb,
+                   void* C, int c_dtype, int64_t ldc,
+                   int64_t M, int64_t N, int64_t K,
+                   int epilogue_id, const float* bias,
+                   const void* aux, int aux_dtype, int64_t ld_aux, int64_t aux_row_mod,
+                   void* aux_out, int64_t ld_aux_out,
+                   int64_t out_group, int64_t out_group_stride, int64_t out_row_offset,
+                   const ReduceJob* job, void* stream) {
     if (!A || !B || !C) return NRV_ERR_NULL;
     if (M <= 0 || N <= 0 || K <= 0) return NRV_ERR_SHAPE;
     if (M > 0x7fffff00ll || N > 0x7fffff00ll || K > 0x7fffff00ll) return NRV_ERR_SHAPE;
@@ -1919,6 +2046,9 @@ extern "C" int nrv_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int64
     p.e.M = (int)M; p.e.N = (int)N;
     p.e.aux_row_mod = (int)aux_row_mod;
     p.e.out_group = (int)out_group; p.e.out_group_stride = (int)out_group_stride; p.e.out_row_offset = (int)out_row_offset;
+    p.job = job ? *job : ReduceJob{};
+    // what a KiB of slabs is taken to cost in shader cycles: NT_SIDE_BYTES_PER_KSTEP per K-step of a 256-row tile (8 x 330 cycles)
+    p.job_cycles_per_kib = (unsigned)(8u * 330u * 1024u / NT_SIDE_BYTES_PER_KSTEP);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool of32 = c_dtype == NRV_F32;
     const bool af32 = aux_dtype == NRV_F32;
@@ -1941,6 +2071,19 @@ extern "C" int nrv_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int64
         default:
             return NRV_ERR_EPILOGUE;
     }
+}
+}  // namespace
+
+extern "C" int nrv_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int64_t ldb,
+                                void* C, int c_dtype, int64_t ldc,
+                                int64_t M, int64_t N, int64_t K,
+                                int epilogue_id, const float* bias,
+                                const void* aux, int aux_dtype, int64_t ld_aux, int64_t aux_row_mod,
+                                void* aux_out, int64_t ld_aux_out,
+                                int64_t out_group, int64_t out_group_stride, int64_t out_row_offset,
+                                void* stream) {
+    return gemm_nt_launch(A, lda, B, ldb, C, c_dtype, ldc, M, N, K, epilogue_id, bias, aux, aux_dtype, ld_aux, aux_row_mod,
+                          aux_out, ld_aux_out, out_group, out_group_stride, out_row_offset, nullptr, stream);
 }
 
 extern "C" int nrv_gemm_nt_plan(int64_t M, int64_t N, int64_t K, int epilogue_id, int remap, nrv_nt_plan* plan) {
@@ -1979,12 +2122,12 @@ extern "C" size_t nrv_gemm_tn_workspace(int64_t M, int64_t N, int64_t T) {
     return (size_t)s * (size_t)M * (size_t)N * 4 + (size_t)s * (size_t)M * 4;   // C slabs (also the beta == 1 single-split case) + bias slabs
 }
 
-extern "C" int nrv_gemm_tn_bf16(const void* A, int64_t lda, const void* B, int64_t ldb,
-                                float* C, int64_t ldc, int64_t M, int64_t N, int64_t T, float beta,
-                                int64_t a_group, int64_t a_group_stride, int64_t a_row_offset,
-                                float* dbias, float dbias_beta,
-                                void* workspace, size_t workspace_bytes, void* stream) {
-    if (!A || !B || !C) return NRV_ERR_NULL;
+extern "C" int nrv_gemm_tn_bf16_deferred(const void* A, int64_t lda, const void* B, int64_t ldb,
+                                         float* C, int64_t ldc, int64_t M, int64_t N, int64_t T, float beta,
+                                         int64_t a_group, int64_t a_group_stride, int64_t a_row_offset,
+                                         float* dbias, float dbias_beta,
+                                         void* workspace, size_t workspace_bytes, nrv_reduce_job* job, void* stream) {
+    if (!A || !B || !C || !job) return NRV_ERR_NULL;
     if (M <= 0 || N <= 0 || T <= 0) return NRV_ERR_SHAPE;
     if (M > 0x7fffff00ll || N > 0x7fffff00ll || T > 0x7fffff00ll) return NRV_ERR_SHAPE;
     if ((M & 7) || (N & 7) || (lda & 7) || (ldb & 7) || lda < M || ldb < N || ldc < N || (ldc & 3)) return NRV_ERR_SHAPE;
@@ -2030,17 +2173,118 @@ extern "C" int nrv_gemm_tn_bf16(const void* A, int64_t lda, const void* B, int64
         hipLaunchKernelGGL(gemm_tn_kernel<TnCfg256>, dim3(p.tiles_mn * splits), dim3(GEMM_THREADS), TnCfg256::LDS, s, p);
     }
     NRV_CHECK_LAUNCH();
-    if (!direct || dbias) {
-        const long long total4 = direct ? (long long)nrv_cdiv(M, 4) : (long long)M * (N >> 2);
-        int blocks = (int)((total4 + 63) / 64);            // 64 chunks of C per block
-        if (blocks > 8192) blocks = 8192;
-        if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s,
-                           direct ? nullptr : static_cast<const float*>(workspace), (long long)M * N, splits, C, (long long)ldc,
-                           (int)M, (int)N, beta, static_cast<const float*>(p.bias_ws), dbias, dbias_beta);
-        NRV_CHECK_LAUNCH();
-    }
+    job->slabs = direct ? nullptr : static_cast<const float*>(workspace);
+    job->slab_stride = (int64_t)M * N;
+    job->splits = splits;
+    job->C = C; job->ldc = ldc; job->M = M; job->N = N; job->beta = beta;
+    job->bias_ws = p.bias_ws; job->dbias = dbias; job->dbias_beta = dbias_beta;
+    job->pending = (!direct || dbias) ? 1 : 0;
     return 0;
+}
+
+namespace {
+ReduceJob device_job(const nrv_reduce_job& j) {
+    ReduceJob d{};
+    d.slabs = j.slabs; d.slab_stride = j.slab_stride; d.C = j.C; d.ldc = j.ldc;
+    d.bias_ws = j.bias_ws; d.dbias = j.dbias;
+    d.splits = j.splits; d.M = (int)j.M; d.N = (int)j.N; d.beta = j.beta; d.dbias_beta = j.dbias_beta;
+    return d;
+}
+// a job as nrv_gemm_tn_bf16_deferred fills it (the fields are the caller's memory: checked again before a kernel reads them)
+int check_job(const nrv_reduce_job* j) {
+    if (!j) return NRV_ERR_NULL;
+    if (!j->pending) return 0;
+    if (!j->slabs && !j->bias_ws) return NRV_ERR_NULL;
+    if (j->M <= 0 || j->N <= 0 || j->M > 0x7fffff00ll || j->N > 0x7fffff00ll || (j->N & 3) || j->splits < 1) return NRV_ERR_SHAPE;
+    if (j->slabs && (!j->C || j->ldc < j->N || (j->ldc & 3) || j->slab_stride < j->M * j->N)) return NRV_ERR_SHAPE;
+    if (j->slabs && (!nrv_aligned16(j->slabs) || !nrv_aligned16(j->C))) return NRV_ERR_ALIGN;
+    if (j->bias_ws && !j->dbias) return NRV_ERR_NULL;
+    return 0;
+}
+}  // namespace
+
+extern "C" int nrv_splitk_reduce(const nrv_reduce_job* job, void* stream) {
+    const int rc = check_job(job);
+    if (rc != 0 || !job->pending) return rc;
+    const bool direct = job->slabs == nullptr;
+    const long long total4 = direct ? (long long)nrv_cdiv(job->M, 4) : (long long)job->M * (job->N >> 2);
+    int blocks = (int)((total4 + 63) / 64);            // 64 chunks of C per block
+    if (blocks > 8192) blocks = 8192;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), device_job(*job));
+    NRV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nrv_gemm_tn_bf16(const void* A, int64_t lda, const void* B, int64_t ldb,
+                                float* C, int64_t ldc, int64_t M, int64_t N, int64_t T, float beta,
+                                int64_t a_group, int64_t a_group_stride, int64_t a_row_offset,
+                                float* dbias, float dbias_beta,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    nrv_reduce_job job{};
+    const int rc = nrv_gemm_tn_bf16_deferred(A, lda, B, ldb, C, ldc, M, N, T, beta, a_group, a_group_stride, a_row_offset,
+                                             dbias, dbias_beta, workspace, workspace_bytes, &job, stream);
+    return rc != 0 ? rc : nrv_splitk_reduce(&job, stream);
+}
+
+namespace {
+// The late-starting workgroups of an NT launch (gemm_nt8_kernel "Late starts against lockstep") and what each would reduce of a job
+// of `job_bytes` slab bytes.  NT_SIDE_BYTES_PER_KSTEP: what such a workgroup reduces in the time of one K-step of a 256-row tile
+// while the other workgroups run their K loops (measured: profiles/r19_nt_side_reduce.txt).
+struct NtSidePlan { int late; long long share_bytes; bool admitted; };
+NtSidePlan nt_side_plan(int64_t M, int64_t N, int64_t K, int epi, bool remap, long long job_bytes) {
+    const NtPlan pl = nt_plan(M, N, K, epi, remap);
+    NtSidePlan sp{0, 0, false};
+    if (!pl.phased || pl.remap || pl.ntiles <= pl.grid || pl.ntiles % pl.grid == 0) return sp;
+    sp.late = pl.grid - pl.ntiles % pl.grid;
+    sp.share_bytes = (job_bytes + sp.late - 1) / sp.late;
+    const long long nk = K / BK;
+    sp.admitted = NRV_TUNE_NT_SIDE_ADMIT(sp.share_bytes <= (long long)NT_SIDE_BYTES_PER_KSTEP * nk * pl.tbm / 256);      // identity in the product (csrc/nrv_dev.hpp)
+    return sp;
+}
+}  // namespace
+
+extern "C" int nrv_gemm_nt_side_plan(int64_t M, int64_t N, int64_t K, int epilogue_id, int remap, int64_t job_bytes,
+                                     nrv_nt_side_plan* plan) {
+    if (!plan) return NRV_ERR_NULL;
+    nrv_nt_plan base;
+    const int rc = nrv_gemm_nt_plan(M, N, K, epilogue_id, remap, &base);
+    if (rc != 0) return rc;
+    if (job_bytes < 0) return NRV_ERR_SHAPE;
+    const NtSidePlan sp = nt_side_plan(M, N, K, epilogue_id, remap != 0, job_bytes);
+    plan->late = sp.late; plan->admitted = sp.admitted ? 1 : 0; plan->share_bytes = sp.share_bytes;
+    return 0;
+}
+
+extern "C" int nrv_gemm_nt_bf16_side(const void* A, int64_t lda, const void* B, int64_t ldb,
+                                     void* C, int c_dtype, int64_t ldc,
+                                     int64_t M, int64_t N, int64_t K,
+                                     int epilogue_id, const float* bias,
+                                     const void* aux, int aux_dtype, int64_t ld_aux, int64_t aux_row_mod,
+                                     void* aux_out, int64_t ld_aux_out,
+                                     int64_t out_group, int64_t out_group_stride, int64_t out_row_offset,
+                                     const nrv_reduce_job* job, int* fused, void* stream) {
+    if (!fused) return NRV_ERR_NULL;
+    *fused = 0;
+    int rc = check_job(job);
+    if (rc != 0) return rc;
+    ReduceJob dj{};
+    if (job->pending && M > 0 && N > 0 && K > 0 && M <= 0x7fffff00ll && N <= 0x7fffff00ll && K <= 0x7fffff00ll) {
+        const long long job_bytes = job->slabs ? (long long)job->splits * job->M * job->N * 4 : 0;
+        if (nt_side_plan(M, N, K, epilogue_id, out_group > 0 || aux_row_mod > 0, job_bytes).admitted) {
+            dj = device_job(*job);
+            *fused = 1;
+        }
+    }
+    if (job->pending && !*fused) {
+        rc = nrv_splitk_reduce(job, stream);
+        if (rc != 0) return rc;
+    }
+    // an argument error of the GEMM leaves a fused job undone: the caller still holds it (*fused is reset)
+    rc = gemm_nt_launch(A, lda, B, ldb, C, c_dtype, ldc, M, N, K, epilogue_id, bias, aux, aux_dtype, ld_aux, aux_row_mod,
+                        aux_out, ld_aux_out, out_group, out_group_stride, out_row_offset, *fused ? &dj : nullptr, stream);
+    if (rc != 0) *fused = 0;
+    return rc;
 }
 
 // ---- grouped stream-K form: all weight gradients of a layer in one launch (gemm_tng_kernel) ----------------------------------

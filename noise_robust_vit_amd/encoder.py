@@ -407,11 +407,25 @@ def _queue(meta: BlockMeta, q: dict) -> None:
         wgrad_flush(meta)
 
 
-def _dw_db(meta: BlockMeta, dy16: Tensor, x16: Tensor, w: Tensor, b: Optional[Tensor], need=None):
+# The slab reduction of a split-K weight gradient as a side job of the dX GEMM that follows it (kernels.gemm_tn defer / gemm_nt side):
+# the late-starting workgroups of the persistent NT kernel reduce the slabs where they would nap.  A token lives in a local list of
+# the half's backward from the weight-gradient launch to the very next NT launch, which takes it (inside its launch, or as a
+# stand-alone reduction in front of it when the library does not admit the job): nothing is ever pending across a
+# `wgrad_flush`, a `wgrad_join`, `sink.layer_done` or a return to autograd, and a backward that raises drops its token with its frame.
+WGRAD_DEFER = True
+
+
+def _take(tok: Optional[list]):
+    """The pending reduction a deferring `_dw_db` left in `tok`, once (None when it did not defer)."""
+    return tok.pop() if tok else None
+
+
+def _dw_db(meta: BlockMeta, dy16: Tensor, x16: Tensor, w: Tensor, b: Optional[Tensor], need=None, defer: Optional[list] = None):
     """Queue the weight and bias gradient of y = x W^T + b (dW = dy^T x on the MFMA, db = colsum(dy) fused into the same kernel).
     Returns (dW, db) as the tensors the launch of `wgrad_flush` will fill: the sink's flat-buffer views, or fresh ones.
     `need` (optional (dW wanted, db wanted)): nothing is queued when neither is wanted (a frozen layer), the bias is left out
-    when only dW is."""
+    when only dW is.  `defer` (a list): with one split-K launch per gradient on the main stream the launch is issued here without
+    its reduction, and the `kernels.PendingReduce` is appended for the caller's next `K.gemm_nt(..., side=_take(defer))`."""
     if need is not None:
         if not need[0] and not need[1]:
             return None, None
@@ -436,6 +450,11 @@ def _dw_db(meta: BlockMeta, dy16: Tensor, x16: Tensor, w: Tensor, b: Optional[Te
     M, N = dy16.shape[1], x16.shape[1]
     out = tw if tw is not None else torch.empty(M, N, dtype=torch.float32, device=dy16.device)
     dbias = None if b is None else (tb if tb is not None else torch.empty(M, dtype=torch.float32, device=dy16.device))
+    if defer is not None and WGRAD_DEFER and not WGRAD_GROUPED and not (meta.sink is not None and _wgrad_on_side(dy16, x16)):
+        wgrad_flush(meta)                # launch order = queue order
+        defer.append(K.gemm_tn(dy16, x16, out=out, beta=bw if tw is not None else 0.0, dbias=dbias,
+                               dbias_beta=bb if tb is not None else 0.0, defer=True)[-1])
+        return out, dbias
     _queue(meta, dict(A=dy16, B=x16, out=out, beta=bw if tw is not None else 0.0, dbias=dbias, dbias_beta=bb if tb is not None else 0.0))
     return out, dbias
 
@@ -643,8 +662,9 @@ def attn_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, B: int,
     _, wo_t = WEIGHTS.get(wo, True)
     _, wqkv_t = WEIGHTS.get(wqkv, True)
     # out-proj:  y = o Wo^T (+bo) (+x)
-    dwo, dbo = _dw_db(meta, dy16, o, wo, bo, None if need is None else need[4:6])
-    do = K.gemm_nt(dy16, wo_t, out_dtype=torch.bfloat16)
+    tok: list = []                       # the weight gradient's pending reduction, taken by the NT launch that follows
+    dwo, dbo = _dw_db(meta, dy16, o, wo, bo, None if need is None else need[4:6], defer=tok)
+    do = K.gemm_nt(dy16, wo_t, out_dtype=torch.bfloat16, side=_take(tok))
     scale = dh ** -0.5
     dmkv = None
     if att.kind == "memory":
@@ -659,9 +679,10 @@ def attn_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, B: int,
         dqkv = K.attn_sinkhorn_bwd(qkv, do, att.lse, att.scal, B, N, H, dh, scale, saved=att.saved)
     else:
         dqkv = K.attn_bwd(qkv, o, do, att.lse, B, N, H, dh, scale)
-    dwqkv, dbqkv = _dw_db(meta, dqkv, xn, wqkv, bqkv, None if need is None else need[2:4])
+    dwqkv, dbqkv = _dw_db(meta, dqkv, xn, wqkv, bqkv, None if need is None else need[2:4], defer=tok)
     if att.kind == "memory":
         dmem = None
+        K.flush_reduce(_take(tok))       # the memory rows' launches below read dwqkv
         if dmkv is not None:
             # dmem = dKV_mem Wkv; dWkv += dKV_mem^T mem (summed over the batch already for shared memories)
             inner = H * dh
@@ -675,9 +696,9 @@ def attn_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, B: int,
     if ln_w is None:                     # no LayerNorm: the projection's input gradient IS the result
         if residual:
             raise NrvError("a residual attention half needs its LayerNorm")
-        dx32 = K.gemm_nt(dqkv, wqkv_t, out_dtype=torch.float32)
+        dx32 = K.gemm_nt(dqkv, wqkv_t, out_dtype=torch.float32, side=_take(tok))
         return dx32, None, [None, None, dwqkv, dbqkv, dwo, dbo]
-    dxn = K.gemm_nt(dqkv, wqkv_t, out_dtype=torch.bfloat16)
+    dxn = K.gemm_nt(dqkv, wqkv_t, out_dtype=torch.bfloat16, side=_take(tok))
     tg, bg = _grad_target(meta, ln_w)
     tb, _ = _grad_target(meta, ln_b)
     if residual and keep is not None and dy32 is None:
@@ -705,9 +726,10 @@ def fc1_gelu(xn: Tensor, w1_b: Tensor, b1: Tensor, q8: bool, save: bool = True):
     return h, u
 
 
-def dgelu_bwd(dy16: Tensor, w2_t: Tensor, u: Tensor) -> Tensor:
-    """du = (dy W2) o gelu', the stream as `fc1_gelu` saved it (bytes or bf16)."""
-    return K.gemm_nt(dy16, w2_t, out_dtype=torch.bfloat16, epilogue=EPI_DGELU_Q8 if u.dtype == torch.uint8 else EPI_DGELU, aux=u)
+def dgelu_bwd(dy16: Tensor, w2_t: Tensor, u: Tensor, side=None) -> Tensor:
+    """du = (dy W2) o gelu', the stream as `fc1_gelu` saved it (bytes or bf16).  `side`: see `kernels.gemm_nt`."""
+    return K.gemm_nt(dy16, w2_t, out_dtype=torch.bfloat16, epilogue=EPI_DGELU_Q8 if u.dtype == torch.uint8 else EPI_DGELU, aux=u,
+                     side=side)
 
 
 def mlp_half_fwd(x: Tensor, meta: BlockMeta, ln_w, ln_b, w1, b1, w2, b2, residual: bool, save: bool = True, drop=None):
@@ -751,10 +773,11 @@ def mlp_half_bwd(dy32: Optional[Tensor], dy16: Optional[Tensor], saved, meta: Bl
         dy16 = K.mask_mul(dy16, keep2, drop_scale)
     _, w2_t = WEIGHTS.get(w2, True)
     _, w1_t = WEIGHTS.get(w1, True)
-    dw2, db2 = _dw_db(meta, dy16, h, w2, b2, None if need is None else need[4:6])
-    du = dgelu_bwd(dy16, w2_t, u)
-    dw1, db1 = _dw_db(meta, du, xn, w1, b1, None if need is None else need[2:4])
-    dxn = K.gemm_nt(du, w1_t, out_dtype=torch.bfloat16)
+    tok: list = []                       # the weight gradient's pending reduction, taken by the NT launch that follows
+    dw2, db2 = _dw_db(meta, dy16, h, w2, b2, None if need is None else need[4:6], defer=tok)
+    du = dgelu_bwd(dy16, w2_t, u, side=_take(tok))
+    dw1, db1 = _dw_db(meta, du, xn, w1, b1, None if need is None else need[2:4], defer=tok)
+    dxn = K.gemm_nt(du, w1_t, out_dtype=torch.bfloat16, side=_take(tok))
     tg, bg = _grad_target(meta, ln_w)
     tb, _ = _grad_target(meta, ln_b)
     dres = (dy32 if dy32 is not None else dy16) if residual else None

@@ -178,11 +178,49 @@ def layernorm_bwd(dy: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: Tens
     return dx32, dx16, dgamma, dbeta
 
 
+def gemm_nt_side_plan(M: int, N: int, K: int, epilogue: int = EPI_NONE, remap: bool = False, job_bytes: int = 0) -> dict:
+    """How `gemm_nt(..., side=...)` would treat a reduction of `job_bytes` slab bytes (include/nrv.h nrv_gemm_nt_side_plan): the
+    late-starting workgroups that take shares, the slab bytes per share, and whether the launch carries the job.  Needs no GPU."""
+    pl = _lib.NtSidePlan()
+    check(_lib.load().nrv_gemm_nt_side_plan(int(M), int(N), int(K), int(epilogue), int(bool(remap)), int(job_bytes),
+                                            ctypes.addressof(pl)), "nrv_gemm_nt_side_plan")
+    return {"late": pl.late, "share_bytes": pl.share_bytes, "admitted": bool(pl.admitted)}
+
+
+class PendingReduce:
+    """The reduction `gemm_tn(..., defer=True)` left behind (include/nrv.h nrv_reduce_job).  Holds the workspace, C and dbias until
+    `gemm_nt(..., side=...)` or `flush_reduce` has put it on a stream; a token that is dropped instead never runs."""
+
+    def __init__(self, job, keep) -> None:
+        self.job, self.keep, self.fused = job, keep, None
+
+    @property
+    def pending(self) -> bool:
+        return self.job is not None and bool(self.job.pending)
+
+    def _consume(self):
+        job, self.job, self.keep = self.job, None, None
+        return job
+
+
+def flush_reduce(pending: Optional[PendingReduce]) -> None:
+    """Run the stand-alone reduction of a deferred weight gradient (nothing when it already ran)."""
+    if pending is None or not pending.pending:
+        return
+    keep = pending.keep
+    job = pending._consume()
+    check(_lib.load().nrv_splitk_reduce(ctypes.addressof(job), _stream()), "nrv_splitk_reduce")      # no LaunchProfile class of its own
+    del keep
+
+
 def gemm_nt(A: Tensor, B: Tensor, *, out_dtype: torch.dtype = torch.bfloat16, epilogue: int = EPI_NONE,
             bias: Optional[Tensor] = None, aux: Optional[Tensor] = None, aux_row_mod: int = 0,
             aux_out: Optional[Tensor] = None, out: Optional[Tensor] = None,
-            out_group: int = 0, out_group_stride: int = 0, out_row_offset: int = 0) -> Tensor:
-    """C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue (include/nrv.h nrv_gemm_nt_bf16)."""
+            out_group: int = 0, out_group_stride: int = 0, out_row_offset: int = 0,
+            side: Optional[PendingReduce] = None) -> Tensor:
+    """C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue (include/nrv.h nrv_gemm_nt_bf16).  `side`: a deferred weight-gradient
+    reduction that this launch completes (nrv_gemm_nt_bf16_side): inside the GEMM launch when the library admits it, as a launch
+    of its own in front of the GEMM otherwise; `side.fused` says which."""
     _bf16(A, "A"); _bf16(B, "B")
     M, K, lda = _rows2d(A, "A")
     N, K2, ldb = _rows2d(B, "B")
@@ -230,6 +268,20 @@ def gemm_nt(A: Tensor, B: Tensor, *, out_dtype: torch.dtype = torch.bfloat16, ep
         nb += M * N * aux.element_size()
     if aux_out is not None:
         nb += M * N * aux_out.element_size()
+    if side is not None and side.pending:
+        keep = side.keep
+        job = side._consume()
+        fused = ctypes.c_int(0)
+        _run("gemm_nt", 2.0 * M * N * K, nb,
+             lambda: lib.nrv_gemm_nt_bf16_side(A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), _dt(out, "out"), ldc,
+                                               M, N, K, int(epilogue), _ptr(bias),
+                                               _ptr(aux), aux_code, ld_aux, int(aux_row_mod),
+                                               _ptr(aux_out), ld_ao, int(out_group), int(out_group_stride), int(out_row_offset),
+                                               ctypes.addressof(job), ctypes.addressof(fused), _stream()),
+             "nrv_gemm_nt_bf16_side")
+        side.fused = bool(fused.value)
+        del keep
+        return out
     _run("gemm_nt", 2.0 * M * N * K, nb,
          lambda: lib.nrv_gemm_nt_bf16(A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), _dt(out, "out"), ldc,
                                       M, N, K, int(epilogue), _ptr(bias),
@@ -242,11 +294,12 @@ def gemm_nt(A: Tensor, B: Tensor, *, out_dtype: torch.dtype = torch.bfloat16, ep
 
 def gemm_tn(A: Tensor, B: Tensor, *, out: Optional[Tensor] = None, beta: float = 0.0,
             a_group: int = 0, a_group_stride: int = 0, a_row_offset: int = 0, T: Optional[int] = None,
-            dbias: Optional[Tensor] = None, dbias_beta: float = 0.0, want_dbias: bool = False):
+            dbias: Optional[Tensor] = None, dbias_beta: float = 0.0, want_dbias: bool = False, defer: bool = False):
     """C[M,N] fp32 = beta*C + sum_t A[t,M] B[t,N]  (weight gradient).  `T` limits the token rows used (default B.shape[0]).
 
     With `want_dbias` (or a `dbias` output) the bias gradient sum_t A[t,:] is produced by the same kernel and the
-    call returns (C, dbias)."""
+    call returns (C, dbias).  With `defer` the slab reduction is not launched (nrv_gemm_tn_bf16_deferred): the call returns its
+    usual result plus a `PendingReduce`, and C / dbias are complete only after `gemm_nt(..., side=...)` or `flush_reduce` took it."""
     _bf16(A, "A"); _bf16(B, "B")
     Ta, M, lda = _rows2d(A, "A")
     Tb, N, ldb = _rows2d(B, "B")
@@ -265,6 +318,16 @@ def gemm_tn(A: Tensor, B: Tensor, *, out: Optional[Tensor] = None, beta: float =
         _f32(dbias, "dbias")
     lib = _lib.load()
     ws = _workspace(lib.nrv_gemm_tn_workspace(M, N, T), A.device)
+    if defer:
+        job = _lib.ReduceJob()
+        _run("gemm_tn", 2.0 * M * N * T, 2 * T * (M + N) + 4 * M * N,
+             lambda: lib.nrv_gemm_tn_bf16_deferred(A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), ldc, M, N, T, float(beta),
+                                                   int(a_group), int(a_group_stride), int(a_row_offset),
+                                                   _ptr(dbias), float(dbias_beta), ws.data_ptr(), ws.numel(),
+                                                   ctypes.addressof(job), _stream()),
+             "nrv_gemm_tn_bf16_deferred")
+        pending = PendingReduce(job, (ws, out, dbias))
+        return (out, dbias, pending) if dbias is not None else (out, pending)
     _run("gemm_tn", 2.0 * M * N * T, 2 * T * (M + N) + 4 * M * N,
          lambda: lib.nrv_gemm_tn_bf16(A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), ldc, M, N, T, float(beta),
                                       int(a_group), int(a_group_stride), int(a_row_offset),

@@ -113,3 +113,9 @@ extern "C" int NRV_DEV_CAT(nrv_dev_read_stamps_, NRV_DEV_TU)(unsigned long long*
 #else
 #define NRV_TUNE_STAGGER(cond) (cond)
 #endif
+// side job of the persistent NT kernel admitted whenever the launch has late workgroups (pair measurements): -DNRV_FORCE_NT_SIDE_ADMIT
+#ifdef NRV_FORCE_NT_SIDE_ADMIT
+#define NRV_TUNE_NT_SIDE_ADMIT(admitted) (true)
+#else
+#define NRV_TUNE_NT_SIDE_ADMIT(admitted) (admitted)
+#endif

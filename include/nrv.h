@@ -667,7 +667,8 @@ int nrv_scatter_rows_f32(const float* dout, const int64_t* index, float* dsrc,
  *   nrv_adamw_f32 : for every i:  g = grad[i] * c,  c = min(1, max_norm / (sqrt(gnorm_sq[0]) + 1e-6))  (c = 1 when gnorm_sq
  *                   is NULL or max_norm <= 0);  p *= 1 - lr * weight_decay;  m = beta1 m + (1 - beta1) g;
  *                   v = beta2 v + (1 - beta2) g^2;  p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
- *                   -- torch.optim.AdamW (amsgrad = False, maximize = False) arithmetic, step >= 1.
+ *                   -- torch.optim.AdamW (amsgrad = False, maximize = False) arithmetic, step >= 1.  A NaN gnorm_sq gives
+ *                   c = NaN (the min lets it through): every p, m and v becomes NaN, as after clip_grad_norm_; +inf gives c = 0.
  *   Hyper-parameters are doubles (1 - beta and the bias corrections are formed in double, then rounded, as torch does).
  *   p, m, v: fp32 [n], 16-byte aligned; grad: fp32 or (ABI 11) bf16 [n] -- the reduced slabs of a bf16 gradient exchange are read in
  *   place, no conversion pass back into an fp32 buffer; gnorm_sq: DEVICE pointer to one float (no host round trip).

@@ -97,7 +97,9 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(float* __restrict__ 
     if (gnorm_sq != nullptr && a.max_norm > 0.f) {
         // clip_grad_norm_: coef = clamp(max_norm / (total_norm + 1e-6), max = 1)
         const float c = a.max_norm / (sqrtf(gnorm_sq[0]) + 1e-6f);
-        coef = c < 1.0f ? c : 1.0f;
+        // the clamp lets a NaN through (c < 1 ? c : 1 would turn a NaN norm into coef = 1 and step the finite elements
+        // unclipped): after clip_grad_norm_ with a NaN norm every gradient, and so every parameter, is NaN
+        coef = !(c >= 1.0f) ? c : 1.0f;
     }
     const long long stride = (long long)gridDim.x * OPT_THREADS;
     for (long long i = (long long)blockIdx.x * OPT_THREADS + threadIdx.x; i < n4; i += stride) {

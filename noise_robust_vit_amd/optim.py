@@ -2,7 +2,8 @@
 
 Counterpart of what the reference harness runs after backward (examples/CIFAR100.py:90-97,191-192; baseline.py:127):
 `torch.nn.utils.clip_grad_norm_(params, 5.0)` followed by `torch.optim.AdamW(...).step()`.  The arithmetic is
-torch.optim.AdamW's (pinned against it in tests/test_optim_gpu.py); the layout is this build's:
+torch.optim.AdamW's (pinned against it in tests/test_optim_gpu.py, per element against float64 in tests/test_optim_edges_gpu.py and,
+behind the trainer with skipped parameters and checkpoints, tests/test_fused_adamw_gpu.py); the layout is this build's:
 
   * gradients already live in ONE flat fp32 buffer (`parallel.GradReducer.flat`, backward order, 16-byte slots);
   * parameters are moved into a second flat buffer with the SAME slot layout (each `param.data` becomes a view, so

@@ -11,8 +11,9 @@ are produced, all max-norm relative to the oracle stream at that stage:
 kernel) shows up as one stage with a large isolated error, while pure rounding-boundary flips give the same small
 isolated error at every stage.
 
-`_Out` is the guarded, NaN-pre-filled output buffer of the per-row edge tests that call the C ABI with buffers they own
-(test_attn_edges_gpu.py, test_sinkhorn_edges_gpu.py).
+`_Out` is the guarded, NaN-pre-filled (or preset) output buffer of the per-row edge tests that call the C ABI with buffers they own
+(test_attn_edges_gpu.py, test_sinkhorn_edges_gpu.py, test_optim_edges_gpu.py); `_moated` puts an input into the middle of a
+NaN-filled storage, so that a read outside it poisons the result (test_twins_kernels_gpu.py, test_optim_edges_gpu.py).
 """
 from __future__ import annotations
 
@@ -25,12 +26,15 @@ PATTERN = {bf: (torch.int16, 0x7FC1), torch.float32: (torch.int32, 0x7FC00001)} 
 
 
 class _Out:
-    """A NaN-filled output of `numel` elements between two guard blocks."""
-    def __init__(self, numel, dtype, dev):
+    """An output of `numel` elements between two guard blocks, NaN-filled or holding `preset` (an in-place operand)."""
+    def __init__(self, numel, dtype, dev, preset=None):
         it, pat = PATTERN[dtype]
         self.raw = torch.full((numel + 2 * GUARD,), pat, dtype=it, device=dev)
         self.t = self.raw.view(dtype)[GUARD:GUARD + numel]
-        self.t.fill_(float("nan"))
+        if preset is None:
+            self.t.fill_(float("nan"))
+        else:
+            self.t.copy_(preset.reshape(-1))
         self.pat = pat
 
     def ptr(self):
@@ -41,6 +45,17 @@ class _Out:
         if written:
             assert not bool(torch.isnan(self.t).any()), f"{what}: an output element was never written"
         return self.t
+
+
+MOAT = 512                                   # elements of NaN in front of and behind every moated input
+
+
+def _moated(t, dev):
+    """A device copy of t in the middle of a NaN-filled storage"""
+    buf = torch.full((t.numel() + 2 * MOAT,), float("nan"), dtype=t.dtype, device=dev)
+    view = buf[MOAT:MOAT + t.numel()].view(t.shape)
+    view.copy_(t)
+    return view
 
 
 def _rel(a: torch.Tensor, b: torch.Tensor) -> float:

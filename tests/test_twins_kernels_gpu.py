@@ -12,13 +12,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import twins_ref as R  # noqa: E402
+from parity_tools import _moated  # noqa: E402        (the NaN-moated input, shared with test_optim_edges_gpu.py)
 
 from noise_robust_vit_amd import kernels as K  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SUB_CASES = [(H, dh, Nq, Nk) for H in R.SUB_HEADS for dh in R.SUB_DH for (Nq, Nk) in R.SUB_SHAPES]
 PEG_CASES = [(H, W, C, ks) for (H, W) in R.PEG_PLANES for C in R.PEG_C for ks in R.PEG_KS]
-MOAT = 512                       # elements of NaN in front of and behind every input
 
 
 @pytest.fixture(scope="module")
@@ -28,14 +28,6 @@ def dev():
 
 def _nan(shape, dtype, dev):
     return torch.full(tuple(shape), float("nan"), dtype=dtype, device=dev)
-
-
-def _moated(t, dev):
-    """A device copy of t in the middle of a NaN-filled storage"""
-    buf = _nan((t.numel() + 2 * MOAT,), t.dtype, dev)
-    view = buf[MOAT:MOAT + t.numel()].view(t.shape)
-    view.copy_(t)
-    return view
 
 
 def _bits(t):

@@ -15,7 +15,9 @@ NT, per record:
         gelu' bf16 stream |u - ref| <= |ref| 2^-8 + 3e-4     bf16 rounding + the erf approximation test_gemm_nt_gelu_stream_8bit allows
         gelu' byte stream |u - ref| <= 0.5 / 202 + 3e-4, h bit-equal to the bf16-stream epilogue's (test_gemm_nt_gelu_stream_8bit)
     The error of torch's own fp32 product against the same float64 reference is printed as a control; the fp32 bound was at
-    least 400 x that control on every record when the table was made (MI355X), so no record documents a tight bound.
+    least 400 x that control on every record when the table was made (MI355X), so no record documents a tight bound
+    here: tests/gemm_epi_ref.py and test_gemm_epi_edges_gpu.py pin the same records per element, bit for bit on exact integer
+    accumulators and within counted bounds for the GELU epilogues.
   * sentinels: C, aux_out and the byte stream live in padded allocations, operands have leading dimensions above K and N;
     nothing outside [0:M, 0:N] changes (odd M: the second row of the last byte-stream pair stays untouched);
   * a second launch of a phased record is bit-identical.

@@ -1,8 +1,15 @@
 """Tensor-level wrappers over the C ABI (include/nrv.h).  No autograd, no fallbacks.
 
 PyTorch is used for device memory (caching allocator) and the current HIP stream only; every
-arithmetic result comes from a kernel in libnrv_hip.so.  All tensors must live on a HIP device
-(`tensor.is_cuda`), be contiguous in their last dimension and 16-byte aligned.
+arithmetic result comes from a kernel in libnrv_hip.so.
+
+The C side sees addresses and integers only, so every wrapper checks what it hands over (tests/launch_audit.py holds them to
+it): each tensor lives on a HIP device (`tensor.is_cuda`), has the dtype its kernel reads, and holds exactly the elements the
+call's dimensions address (at least, where a docstring says so).  Tensors are contiguous, compared by element count and not
+by shape; the exceptions are the operands documented as row-major views (GEMM operands, q / k / v views, `u` of GEGLU, ...),
+whose row stride is passed on with unit stride in the last dimension.  An input that callers pass strided is copied where the
+docstring or the code says `.contiguous()`; an output or a saved statistic never is.  The checks compare attributes and never
+read device memory.  16-byte alignment is the C side's rule.
 """
 from __future__ import annotations
 
@@ -53,6 +60,27 @@ def _rows2d(t: Tensor, name: str) -> Tuple[int, int, int]:
     if t.dim() != 2 or t.stride(1) != 1:
         raise NrvError(f"{name} must be 2-D with contiguous rows, got shape {tuple(t.shape)} stride {t.stride()}")
     return t.shape[0], t.shape[1], t.stride(0)
+
+
+def _dense(t: Tensor, name: str, dtype: Optional[torch.dtype], n: int, by: str = "the call's dimensions") -> None:
+    """`t` is on the device, of `dtype` (None: fp32 or bf16), contiguous, and holds exactly `n` elements; `by` names what `n`
+    was taken from, for the message.  Element counts, not shapes: the kernels address flat buffers and callers pass reshaped
+    views of them.  Attribute comparisons only."""
+    _dev(t, name)
+    if dtype is None:
+        _dt(t, name)
+    elif t.dtype != dtype:
+        raise NrvError(f"{name} must be {dtype}, got {t.dtype}")
+    if t.numel() != n or not t.is_contiguous():
+        raise NrvError(f"{name} must be contiguous with {n} elements (by {by}), got shape {tuple(t.shape)} stride {t.stride()}")
+
+
+def _view2d(t: Tensor, name: str, rows: int, width: int) -> int:
+    """Row stride of a bf16 [rows, >= width] view with unit column stride (a column block of a wider buffer works)."""
+    _bf16(t, name)
+    if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != rows or t.shape[1] < width or (rows > 1 and t.stride(0) < t.shape[1]):
+        raise NrvError(f"{name} must be a row-major bf16 [{rows}, >= {width}] view, got shape {tuple(t.shape)} stride {t.stride()}")
+    return t.stride(0)
 
 
 def _ptr(t: Optional[Tensor]) -> Optional[int]:
@@ -138,9 +166,10 @@ def _run(name: str, flops: float, nbytes: float, call, what: str) -> None:
 # ----------------------------------------------------------------------------------------------
 def layernorm_fwd(x: Tensor, gamma: Tensor, beta: Tensor, eps: float):
     """x [rows, dim] fp32|bf16 -> (y bf16, mean fp32, rstd fp32).  nn.LayerNorm (simple_vit.py:38,54; vit.py:104,115)."""
-    _dev(x, "x"); _f32(gamma, "gamma"); _f32(beta, "beta")
+    _dev(x, "x")
     x = x.contiguous()
     rows, dim = x.shape
+    _dense(gamma, "gamma", torch.float32, dim, "x"); _dense(beta, "beta", torch.float32, dim, "x")
     y = torch.empty(rows, dim, dtype=torch.bfloat16, device=x.device)
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
@@ -156,15 +185,24 @@ def layernorm_bwd(dy: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: Tens
                   want_f32: bool = True, want_bf16: bool = False,
                   dgamma: Optional[Tensor] = None, dbeta: Optional[Tensor] = None, accumulate: bool = False):
     """Returns (dx_f32|None, dx_bf16|None, dgamma, dbeta); dx = dres + LN'(dy)."""
-    _bf16(dy, "dy"); _dev(x, "x"); _f32(gamma, "gamma")
+    _dev(x, "x")
+    x = x.contiguous()                      # as layernorm_fwd took it
     rows, dim = x.shape
+    _dense(dy, "dy", torch.bfloat16, rows * dim, "x"); _dense(gamma, "gamma", torch.float32, dim, "x")
+    _dense(mean, "mean", torch.float32, rows, "x"); _dense(rstd, "rstd", torch.float32, rows, "x")
+    if dres is not None:
+        _dense(dres, "dres", None, rows * dim, "x")
     lib = _lib.load()
     dx32 = torch.empty(rows, dim, dtype=torch.float32, device=x.device) if want_f32 else None
     dx16 = torch.empty(rows, dim, dtype=torch.bfloat16, device=x.device) if want_bf16 else None
     if dgamma is None:
         dgamma = torch.empty(dim, dtype=torch.float32, device=x.device); accumulate = False
+    else:
+        _dense(dgamma, "dgamma", torch.float32, dim, "x")
     if dbeta is None:
         dbeta = torch.empty(dim, dtype=torch.float32, device=x.device)
+    else:
+        _dense(dbeta, "dbeta", torch.float32, dim, "x")
     wsb = lib.nrv_layernorm_bwd_workspace(rows, dim)
     ws = _workspace(wsb, x.device)
     nb = rows * dim * (2 + x.element_size() + (dres.element_size() if dres is not None else 0)
@@ -230,6 +268,7 @@ def gemm_nt(A: Tensor, B: Tensor, *, out_dtype: torch.dtype = torch.bfloat16, ep
         if out_group:
             raise NrvError("gemm_nt: an output row remap needs a caller-provided `out`")
         out = torch.empty(M, N, dtype=out_dtype, device=A.device)
+    _dev(out, "out")
     _, _, ldc = _rows2d(out, "out")
     ld_aux = 0
     aux_code = 0
@@ -259,9 +298,11 @@ def gemm_nt(A: Tensor, B: Tensor, *, out_dtype: torch.dtype = torch.bfloat16, ep
                 raise NrvError("gemm_nt: EPI_BIAS_GELU_Q8 writes the gelu' stream as uint8 in row pairs: M rounded up to even rows, N % 64 == 0")
         else:
             _bf16(aux_out, "aux_out")
-        _, _, ld_ao = _rows2d(aux_out, "aux_out")
+        orows, ocols, ld_ao = _rows2d(aux_out, "aux_out")
+        if orows < M or ocols < N:
+            raise NrvError(f"gemm_nt: aux_out is [{orows}, {ocols}], the epilogue writes [{M}, {N}]")
     if bias is not None:
-        _f32(bias, "bias")
+        _dense(bias, "bias", torch.float32, N, "B")
     lib = _lib.load()
     nb = 2 * (M * K + N * K) + M * N * out.element_size()
     if aux is not None and not aux_row_mod:
@@ -305,17 +346,21 @@ def gemm_tn(A: Tensor, B: Tensor, *, out: Optional[Tensor] = None, beta: float =
     Tb, N, ldb = _rows2d(B, "B")
     T = Tb if T is None else T
     if a_group == 0 and Ta != Tb:
-        raise NrvError(f"gemm_tn: token count mismatch {Ta} vs {Tb}")
+        raise NrvError(f"gemm_tn: token count mismatch, A has {Ta} rows and B {Tb}")
+    if T > Tb:
+        raise NrvError(f"gemm_tn: T = {T} token rows, B has {Tb}")
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=A.device)
         beta = 0.0
     _f32(out, "out")
-    _, _, ldc = _rows2d(out, "out")
+    orows, ocols, ldc = _rows2d(out, "out")
+    if orows < M or ocols < N:
+        raise NrvError(f"gemm_tn: out is [{orows}, {ocols}], the gradient is [{M}, {N}]")
     if want_dbias and dbias is None:
         dbias = torch.empty(M, dtype=torch.float32, device=A.device)
         dbias_beta = 0.0
     if dbias is not None:
-        _f32(dbias, "dbias")
+        _dense(dbias, "dbias", torch.float32, M, "A")
     lib = _lib.load()
     ws = _workspace(lib.nrv_gemm_tn_workspace(M, N, T), A.device)
     if defer:
@@ -395,6 +440,8 @@ def colsum(X: Tensor, *, out: Optional[Tensor] = None, beta: float = 0.0) -> Ten
     if out is None:
         out = torch.empty(N, dtype=torch.float32, device=X.device)
         beta = 0.0
+    else:
+        _dense(out, "out", torch.float32, N, "X")
     lib = _lib.load()
     ws = _workspace(lib.nrv_colsum_workspace(T, N), X.device)
     _run("colsum", 0.0, 2 * T * N,
@@ -422,11 +469,16 @@ def attn_fwd(qkv: Tensor, B: int, N: int, H: int, dh: int, scale: float, layout:
     return out, lse
 
 
+def _attn_bwd_args(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, B: int, N: int, H: int, dh: int) -> None:
+    """What every attention backward over a packed qkv is handed: qkv [B*N, 3*H*dh], out and dout [B*N, H*dh], lse [B, H, N]."""
+    _dense(qkv, "qkv", torch.bfloat16, B * N * 3 * H * dh)
+    _dense(out, "out", torch.bfloat16, B * N * H * dh); _dense(dout, "dout", torch.bfloat16, B * N * H * dh)
+    _dense(lse, "lse", torch.float32, B * H * N)
+
+
 def attn_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, B: int, N: int, H: int, dh: int, scale: float,
              layout: int = 0) -> Tensor:
-    _bf16(qkv, "qkv"); _bf16(out, "out"); _bf16(dout, "dout"); _f32(lse, "lse")
-    if not (qkv.is_contiguous() and out.is_contiguous() and dout.is_contiguous()):
-        raise NrvError("attn_bwd: operands must be contiguous")
+    _attn_bwd_args(qkv, out, dout, lse, B, N, H, dh)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(B * H * N, dtype=torch.float32, device=qkv.device)
     lib = _lib.load()
@@ -468,9 +520,7 @@ def attn_drop_fwd(qkv: Tensor, seed: Tensor, p: float, B: int, N: int, H: int, d
 
 def attn_drop_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, seed: Tensor, p: float, B: int, N: int, H: int, dh: int,
                   scale: float) -> Tensor:
-    _bf16(qkv, "qkv"); _bf16(out, "out"); _bf16(dout, "dout"); _f32(lse, "lse"); _seed64(seed, "seed")
-    if not (qkv.is_contiguous() and out.is_contiguous() and dout.is_contiguous()):
-        raise NrvError("attn_drop_bwd: operands must be contiguous")
+    _attn_bwd_args(qkv, out, dout, lse, B, N, H, dh); _seed64(seed, "seed")
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(B * H * N, dtype=torch.float32, device=qkv.device)
     lib = _lib.load()
@@ -491,7 +541,7 @@ def attn_drop_mask(seed: Tensor, p: float, B: int, H: int, N: int) -> Tensor:
 
 def attn_probs(qkv: Tensor, lse: Tensor, B: int, N: int, H: int, dh: int, scale: float, layout: int = 0) -> Tensor:
     """fp32 [B, H, N, N] softmax probabilities recomputed from q, k and the saved log-sum-exp (introspection only)."""
-    _bf16(qkv, "qkv"); _f32(lse, "lse")
+    _dense(qkv, "qkv", torch.bfloat16, B * N * 3 * H * dh); _dense(lse, "lse", torch.float32, B * H * N)
     probs = torch.empty(B, H, N, N, dtype=torch.float32, device=qkv.device)
     check(_lib.load().nrv_attn_probs(qkv.data_ptr(), lse.data_ptr(), probs.data_ptr(), B, N, H, dh, float(scale), int(layout), _stream()),
           "nrv_attn_probs")
@@ -530,14 +580,25 @@ def mask_pack(mask: Tensor, B: int, H: int, Nq: int, Nk: int) -> MaskBits:
     return MaskBits(bits, Nq, Nk, mh * Nq * W if mb > 1 else 0, Nq * W if mh > 1 else 0)
 
 
-def _mem_args(mkv: Optional[Tensor], M: int, shared: bool, mask: Optional[MaskBits], Nq: int, H: int, dh: int):
+def _mem_args(mkv: Optional[Tensor], B: int, M: int, shared: bool, mask: Optional[MaskBits], Nq: int, H: int, dh: int):
     if M > 0:
-        _bf16(mkv, "mem_kv")
-        rows, cols, ld = _rows2d(mkv, "mem_kv")
-        if cols != 2 * H * dh or ld != cols or rows < M:
-            raise NrvError(f"mem_kv must be contiguous [*, {2 * H * dh}] with at least {M} rows")
-    if mask is not None and (mask.Nq != Nq or mask.Nk != Nq + M):
-        raise NrvError(f"mask packed for [{mask.Nq}, {mask.Nk}], attention is [{Nq}, {Nq + M}]")
+        if mkv is None:
+            raise NrvError(f"mkv: {M} memory keys need their mem_kv tensor")
+        _bf16(mkv, "mkv")
+        rows, cols, ld = _rows2d(mkv, "mkv")
+        if cols != 2 * H * dh or ld != cols or rows < (M if shared else B * M):
+            raise NrvError(f"mkv (mem_kv) must be contiguous [*, {2 * H * dh}] with at least {M if shared else B * M} rows, got "
+                           f"{tuple(mkv.shape)} stride {mkv.stride()}")
+    if mask is not None:
+        if mask.Nq != Nq or mask.Nk != Nq + M:
+            raise NrvError(f"mask packed for [{mask.Nq}, {mask.Nk}], attention is [{Nq}, {Nq + M}]")
+        W = (mask.Nk + 31) // 32
+        bits = mask.bits
+        _dev(bits, "mask.bits")
+        if bits.dtype != torch.int32 or not bits.is_contiguous() or min(mask.bstride, mask.hstride) < 0 \
+                or bits.numel() < (B - 1) * mask.bstride + (H - 1) * mask.hstride + Nq * W:
+            raise NrvError(f"mask.bits must be contiguous int32 words covering batch stride {mask.bstride}, head stride {mask.hstride} "
+                           f"and {Nq} rows of {W}, got {bits.dtype} {tuple(bits.shape)} stride {bits.stride()}")
     mptr = mkv.data_ptr() if M > 0 else None
     kptr, bs, hs = (mask.bits.data_ptr(), mask.bstride, mask.hstride) if mask is not None else (None, 0, 0)
     return mptr, 0 if shared else M, kptr, bs, hs
@@ -551,8 +612,8 @@ def attn_mem_fwd(qkv: Tensor, mkv: Optional[Tensor], B: int, Nq: int, M: int, H:
     if not qkv.is_contiguous() or qkv.numel() != B * Nq * 3 * H * dh:
         raise NrvError("attn_mem_fwd: qkv must be contiguous [B*Nq, 3*H*dh]")
     if M > 0 and not shared and mkv is not None and mkv.shape[0] != B * M:
-        raise NrvError("attn_mem_fwd: per-sample memories need B*M rows")
-    mptr, mstride, kptr, bs, hs = _mem_args(mkv, M, shared, mask, Nq, H, dh)
+        raise NrvError("attn_mem_fwd: per-sample memories need B*M rows of mkv")
+    mptr, mstride, kptr, bs, hs = _mem_args(mkv, B, M, shared, mask, Nq, H, dh)
     out = torch.empty(B * Nq, H * dh, dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty(B, H, Nq, dtype=torch.float32, device=qkv.device)
     Nk = Nq + M
@@ -568,10 +629,8 @@ def attn_mem_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, mkv: Optio
                  dh: int, scale: float, shared: bool = True, mask: Optional[MaskBits] = None):
     """-> (dqkv bf16 [B*Nq, 3*H*dh], dmem_kv fp32 [M, 2*H*dh] summed over the batch (shared) / [B*M, 2*H*dh] (per sample),
     None when M == 0)."""
-    _bf16(qkv, "qkv"); _bf16(out, "out"); _bf16(dout, "dout"); _f32(lse, "lse")
-    if not (qkv.is_contiguous() and out.is_contiguous() and dout.is_contiguous() and lse.is_contiguous()):
-        raise NrvError("attn_mem_bwd: operands must be contiguous")
-    mptr, mstride, kptr, bs, hs = _mem_args(mkv, M, shared, mask, Nq, H, dh)
+    _attn_bwd_args(qkv, out, dout, lse, B, Nq, H, dh)
+    mptr, mstride, kptr, bs, hs = _mem_args(mkv, B, M, shared, mask, Nq, H, dh)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(B * H * Nq, dtype=torch.float32, device=qkv.device)
     dmem = torch.empty(B * M, 2 * H * dh, dtype=torch.float32, device=qkv.device) if M > 0 else None
@@ -619,9 +678,8 @@ def attn_sinkhorn_fwd(qkv: Tensor, B: int, N: int, H: int, dh: int, scale: float
 
 def attn_sinkhorn_bwd(qkv: Tensor, dout: Tensor, lse: Tensor, scal: Tensor, B: int, N: int, H: int, dh: int, scale: float,
                       saved: Optional[dict] = None) -> Tensor:
-    _bf16(qkv, "qkv"); _bf16(dout, "dout"); _f32(lse, "lse"); _f32(scal, "scal")
-    if not (qkv.is_contiguous() and dout.is_contiguous()):
-        raise NrvError("attn_sinkhorn_bwd: operands must be contiguous")
+    _dense(qkv, "qkv", torch.bfloat16, B * N * 3 * H * dh); _dense(dout, "dout", torch.bfloat16, B * N * H * dh)
+    _dense(lse, "lse", torch.float32, B * H * N); _dense(scal, "scal", torch.float32, B * H * 7 * N)
     if not _sinkhorn_fused_shape(N, dh):
         return _attn_sinkhorn_bwd_composed(qkv, dout, lse, scal, B, N, H, dh, scale, saved)
     dqkv = torch.empty_like(qkv)
@@ -827,11 +885,11 @@ def _keep_mask(keep: Tensor, like: Tensor, what: str) -> None:
 
 def dropout_add(x: Tensor, y: Tensor, keep: Tensor, scale: float, out: Optional[Tensor] = None) -> Tensor:
     """out = x + y * (keep ? scale : 0): the fp32 residual stream takes a dropped branch output (include/nrv.h nrv_dropout_add_f32)."""
-    _f32(x, "x"); _f32(y, "y")
-    if not (x.is_contiguous() and y.is_contiguous()) or x.shape != y.shape:
-        raise NrvError("dropout_add: x and y must be contiguous fp32 tensors of one shape")
+    _dense(x, "x", torch.float32, x.numel()); _dense(y, "y", torch.float32, x.numel(), "x")
     _keep_mask(keep, x, "dropout_add")
     o = torch.empty_like(x) if out is None else out
+    if out is not None:
+        _dense(out, "out", torch.float32, x.numel(), "x")
     lib = _lib.load()
     _run("dropout", 0.0, x.numel() * 13,
          lambda: lib.nrv_dropout_add_f32(x.data_ptr(), y.data_ptr(), keep.data_ptr(), o.data_ptr(), float(scale), x.numel(), _stream()),
@@ -841,11 +899,11 @@ def dropout_add(x: Tensor, y: Tensor, keep: Tensor, scale: float, out: Optional[
 
 def mask_mul(a: Tensor, keep: Tensor, scale: float, out: Optional[Tensor] = None) -> Tensor:
     """out = a * (keep ? scale : 0) on bf16 tensors (include/nrv.h nrv_mask_mul_bf16); `out=a` works in place."""
-    _bf16(a, "a")
-    if not a.is_contiguous():
-        raise NrvError("mask_mul: a must be contiguous")
+    _dense(a, "a", torch.bfloat16, a.numel())
     _keep_mask(keep, a, "mask_mul")
     o = torch.empty_like(a) if out is None else out
+    if out is not None:
+        _dense(out, "out", torch.bfloat16, a.numel(), "a")
     lib = _lib.load()
     _run("dropout", 0.0, a.numel() * 5,
          lambda: lib.nrv_mask_mul_bf16(a.data_ptr(), keep.data_ptr(), o.data_ptr(), float(scale), a.numel(), _stream()),
@@ -855,10 +913,10 @@ def mask_mul(a: Tensor, keep: Tensor, scale: float, out: Optional[Tensor] = None
 
 def mask_mul_f32(a: Tensor, keep: Tensor, scale: float, out: Optional[Tensor] = None) -> Tensor:
     """out = a * (keep ? scale : 0) on fp32 tensors of any size (include/nrv.h nrv_mask_mul_f32)."""
-    _f32(a, "a"); _dev(keep, "keep")
-    if not a.is_contiguous() or keep.dtype != torch.uint8 or not keep.is_contiguous() or keep.numel() != a.numel():
-        raise NrvError("mask_mul_f32: a contiguous fp32, keep a contiguous uint8 mask with one byte per element")
+    _dense(a, "a", torch.float32, a.numel()); _dense(keep, "keep", torch.uint8, a.numel(), "a")
     o = torch.empty_like(a) if out is None else out
+    if out is not None:
+        _dense(out, "out", torch.float32, a.numel(), "a")
     lib = _lib.load()
     _run("dropout", 0.0, a.numel() * 9,
          lambda: lib.nrv_mask_mul_f32(a.data_ptr(), keep.data_ptr(), o.data_ptr(), float(scale), a.numel(), _stream()), "nrv_mask_mul_f32")
@@ -902,8 +960,11 @@ def sumsq_workspace(n: int) -> int:
 
 def sumsq(x: Tensor, out: Tensor, ws: Tensor) -> None:
     """out[0] = sum(x^2) for a flat fp32 or bf16 buffer (deterministic); ws: fp32 scratch of nrv_sumsq_workspace bytes."""
-    _dev(x, "x")
+    _dense(x, "x", None, x.numel()); _dense(out, "out", torch.float32, 1)
     lib = _lib.load()
+    _dev(ws, "ws")
+    if ws.dtype != torch.float32 or not ws.is_contiguous() or ws.numel() * 4 < lib.nrv_sumsq_workspace(x.numel()):
+        raise NrvError(f"sumsq: ws must be contiguous fp32 scratch of nrv_sumsq_workspace({x.numel()}) bytes, got {ws.dtype} {tuple(ws.shape)}")
     _run("optimizer", 0.0, x.numel() * x.element_size(),
          lambda: lib.nrv_sumsq_f32(x.data_ptr(), _dt(x, "x"), x.numel(), out.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
          "nrv_sumsq_f32")
@@ -915,11 +976,14 @@ def adamw_flat(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, beta1: flo
     """In-place clip + AdamW on flat buffers (include/nrv.h: nrv_adamw_f32): p, m, v fp32; g fp32 or bf16 (the reduced slabs of a
     bf16 gradient exchange, read in place).  `step_scalars`: device tensor of 3 floats that replaces the step-dependent scalars
     (graph replay)."""
-    for t, n in ((p, "p"), (m, "m"), (v, "v")):
-        _f32(t, n)
-    _dev(g, "g")
-    if not (p.numel() == g.numel() == m.numel() == v.numel()):
-        raise NrvError("adamw_flat: buffers differ in length")
+    n = p.numel()
+    _dense(p, "p", torch.float32, n); _dense(m, "m", torch.float32, n, "p"); _dense(v, "v", torch.float32, n, "p"); _dense(g, "g", None, n, "p")
+    if gnorm_sq is not None:
+        _dense(gnorm_sq, "gnorm_sq", torch.float32, 1)
+    if step_scalars is not None:
+        _dev(step_scalars, "step_scalars")
+        if step_scalars.dtype != torch.float32 or not step_scalars.is_contiguous() or step_scalars.numel() < 3:
+            raise NrvError(f"step_scalars must hold at least 3 contiguous fp32 values, got {step_scalars.dtype} {tuple(step_scalars.shape)}")
     lib = _lib.load()
     _run("optimizer", 0.0, p.numel() * (24 + g.element_size()),
          lambda: lib.nrv_adamw_f32(p.data_ptr(), g.data_ptr(), _dt(g, "g"), m.data_ptr(), v.data_ptr(), p.numel(),
@@ -952,10 +1016,16 @@ def sinkhorn_fwd(scores: Tensor, iters: int = SINKHORN_ITERS):
 
 def sinkhorn_bwd(scores: Tensor, dout: Tensor, lse: Tensor, avec: Tensor, bvec: Tensor, iters: int = SINKHORN_ITERS) -> Tensor:
     _f32(scores, "scores"); _f32(dout, "dout")
+    if scores.dim() < 2:
+        raise NrvError("sinkhorn_bwd: scores must have at least two dimensions")
     s = scores.contiguous()
-    d = dout.contiguous()
     R, C = s.shape[-2], s.shape[-1]
     G = s.numel() // (R * C)
+    if dout.numel() != s.numel():
+        raise NrvError(f"sinkhorn_bwd: dout has {dout.numel()} elements, scores {s.numel()}")
+    d = dout.contiguous()
+    _dense(lse, "lse", torch.float32, G * R, "scores"); _dense(avec, "avec", torch.float32, G * (iters + 1) * R, "scores and iters")
+    _dense(bvec, "bvec", torch.float32, G * max(iters, 1) * C, "scores and iters")
     ds = torch.empty_like(s)
     lib = _lib.load()
     _run("sinkhorn_norm_bwd", 0.0, s.numel() * 4 * (4 * iters + 6),
@@ -978,11 +1048,13 @@ def build_cast_jobs(jobs):
     if not jobs:
         return None
     rows, start = [], 0
-    for w, wb, wt in jobs:
-        _f32(w, "w"); _bf16(wb, "wb")
-        if not (w.is_contiguous() and wb.is_contiguous() and (wt is None or wt.is_contiguous())):
-            raise NrvError("cast jobs need contiguous tensors")
+    for i, (w, wb, wt) in enumerate(jobs):
+        if w.dim() != 2:
+            raise NrvError(f"jobs[{i}]: w must be fp32 [R, C], got {tuple(w.shape)}")
         R, C = w.shape
+        _dense(w, f"jobs[{i}] w", torch.float32, R * C); _dense(wb, f"jobs[{i}] wb", torch.bfloat16, R * C, "w")
+        if wt is not None:
+            _dense(wt, f"jobs[{i}] wt", torch.bfloat16, R * C, "w")
         tiles_c = (C + 63) // 64
         rows.append((w.data_ptr(), wb.data_ptr(), 0 if wt is None else wt.data_ptr(), R, C, start, tiles_c))
         start += ((R + 63) // 64) * tiles_c
@@ -1040,10 +1112,12 @@ def window_attn_bwd(qkv: Tensor, table: Tensor, dout: Tensor, stats: Tensor, B: 
     _window_args(qkv, B, pH, pW, C, heads, Wh, Ww, sh, sw)
     _bf16(dout, "dout"); _f32(stats, "stats"); _f32(table, "table")
     T = B * pH * pW
+    if tuple(table.shape) != ((2 * Wh - 1) * (2 * Ww - 1), heads) or not table.is_contiguous():
+        raise NrvError(f"window_attn: table must be contiguous [{(2 * Wh - 1) * (2 * Ww - 1)}, {heads}], got {tuple(table.shape)}")
     if not dout.is_contiguous() or tuple(dout.shape) != (T, C):
         raise NrvError(f"window_attn_bwd: dout must be contiguous [{T}, {C}], got {tuple(dout.shape)}")
-    if tuple(stats.shape) != (T, heads, 8 if robust else 1):
-        raise NrvError(f"window_attn_bwd: stats {tuple(stats.shape)} do not belong to this call")
+    if tuple(stats.shape) != (T, heads, 8 if robust else 1) or not stats.is_contiguous():
+        raise NrvError(f"window_attn_bwd: stats {tuple(stats.shape)} stride {stats.stride()} do not belong to this call")
     lib = _lib.load()
     wsb = lib.nrv_window_attn_bwd_workspace(B, pH, pW, C, heads, Wh, Ww)
     ws = _workspace(wsb, qkv.device)
@@ -1058,10 +1132,10 @@ def window_attn_bwd(qkv: Tensor, table: Tensor, dout: Tensor, stats: Tensor, B: 
     return dqkv, dtable
 
 
-def _sd_args(x: Tensor, keep: Tensor, survival: float) -> Tuple[int, int]:
+def _sd_args(x: Tensor, name: str, keep: Tensor, survival: float) -> Tuple[int, int]:
     _f32(keep, "keep")
     if not x.is_contiguous() or x.dim() != 2 or x.shape[1] % 4:
-        raise NrvError("stochastic depth: a contiguous [rows, dim] tensor with dim % 4 == 0")
+        raise NrvError(f"stochastic depth: {name} must be a contiguous [rows, dim] tensor with dim % 4 == 0, got {tuple(x.shape)}")
     if keep.dim() != 1 or not keep.is_contiguous() or x.shape[0] % keep.numel():
         raise NrvError(f"stochastic depth: keep must be one value per sample, {keep.numel()} does not divide {x.shape[0]} rows")
     if not survival > 0.0:
@@ -1072,10 +1146,11 @@ def _sd_args(x: Tensor, keep: Tensor, survival: float) -> Tuple[int, int]:
 def sd_add(x: Tensor, y: Tensor, keep: Tensor, survival: float, out: Optional[Tensor] = None) -> Tensor:
     """out = x + y * keep[sample] / survival (include/nrv.h nrv_sd_add_f32)."""
     _f32(x, "x"); _f32(y, "y")
-    rows, per = _sd_args(x, keep, survival)
-    if y.shape != x.shape or not y.is_contiguous():
-        raise NrvError("sd_add: y must match x")
+    rows, per = _sd_args(x, "x", keep, survival)
+    _dense(y, "y", torch.float32, x.numel(), "x")
     o = torch.empty_like(x) if out is None else out
+    if out is not None:
+        _dense(out, "out", torch.float32, x.numel(), "x")
     _run("sd_add", 0.0, x.numel() * 12,
          lambda: _lib.load().nrv_sd_add_f32(x.data_ptr(), y.data_ptr(), keep.data_ptr(), o.data_ptr(), float(survival), rows, per,
                                             x.shape[1], _stream()), "nrv_sd_add_f32")
@@ -1085,7 +1160,7 @@ def sd_add(x: Tensor, y: Tensor, keep: Tensor, survival: float, out: Optional[Te
 def sd_scale_bf16(dy: Tensor, keep: Tensor, survival: float) -> Tensor:
     """bf16(dy * keep[sample] / survival): the branch gradient of sd_add (include/nrv.h nrv_sd_scale_bf16)."""
     _f32(dy, "dy")
-    rows, per = _sd_args(dy, keep, survival)
+    rows, per = _sd_args(dy, "dy", keep, survival)
     o = torch.empty(dy.shape, dtype=torch.bfloat16, device=dy.device)
     _run("sd_scale", 0.0, dy.numel() * 6,
          lambda: _lib.load().nrv_sd_scale_bf16(dy.data_ptr(), keep.data_ptr(), o.data_ptr(), float(survival), rows, per,
@@ -1165,9 +1240,9 @@ def bn_bwd(dz: Tensor, y: Tensor, mean: Tensor, scale: Tensor, gamma: Tensor, be
            training: bool = True):
     """Backward of bn_apply without the residual (include/nrv.h nrv_bn_bwd): returns (dy bf16 [T, C], dgamma, dbeta)."""
     T, C = _bn_rows(y, "y")
-    _dev(dz, "dz")
-    if dz.shape != y.shape or not dz.is_contiguous():
-        raise NrvError("bn_bwd: dz must match y")
+    _dense(dz, "dz", None, T * C, "y")
+    for t, n in ((mean, "mean"), (scale, "scale"), (gamma, "gamma"), (beta, "beta")):
+        _dense(t, n, torch.float32, C, "y")
     per = _bn_keep(keep, T)
     dy = torch.empty(T, C, dtype=torch.bfloat16, device=y.device)
     dg = torch.empty(C, dtype=torch.float32, device=y.device)
@@ -1231,7 +1306,9 @@ def bias_index(idx: Tensor, n_offsets: int, device) -> BiasIndex:
     """Build the int32 index and its inverse from an int64 [Nq, Nk] attention_bias_idxs (host arithmetic, once per geometry).
     Entries outside [0, n_offsets) are refused here, before any kernel reads them."""
     import numpy as np
-    a = idx.detach().to("cpu", torch.int64).numpy()       # numpy, not torch: nothing here is dispatched as a (capturable) op
+    if idx.dtype != torch.int64:
+        raise NrvError(f"bias index (idx) must be int64, got {idx.dtype}")
+    a = idx.detach().to("cpu").numpy()                    # numpy, not torch: nothing here is dispatched as a (capturable) op
     if a.ndim != 2:
         raise NrvError(f"bias index must be [Nq, Nk], got {a.shape}")
     if a.size and (int(a.min()) < 0 or int(a.max()) >= n_offsets):
@@ -1244,23 +1321,32 @@ def bias_index(idx: Tensor, n_offsets: int, device) -> BiasIndex:
                      torch.from_numpy(order).to(device), int(n_offsets))
 
 
-def _qkv_view(t: Tensor, rows: int, name: str) -> int:
-    _bf16(t, name)
-    if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != rows:
-        raise NrvError(f"bias_attn: {name} must be a row-major [{rows}, *] view, got {tuple(t.shape)}")
-    return t.stride(0)
+def _bias_attn_args(q: Tensor, k: Tensor, v: Tensor, hq: int, hk: int, hv: int, table: Tensor, index: BiasIndex,
+                    B: int, H: int, Nq: int, Nk: int, kd: int, d: int, pre: str = "") -> Tuple[int, int, int]:
+    """Row strides of the q / k / v views (or of the gradient views `pre` = "d"): head h's columns [h*step, h*step + width) must
+    lie inside the view.  The table and the index belong to (H, Nq, Nk)."""
+    if min(hq, hk, hv) < 0:
+        raise NrvError(f"bias_attn: negative head steps ({hq}, {hk}, {hv})")
+    lds = (_view2d(q, pre + "q", B * Nq, (H - 1) * hq + kd), _view2d(k, pre + "k", B * Nk, (H - 1) * hk + kd),
+           _view2d(v, pre + "v", B * Nk, (H - 1) * hv + d))
+    if pre:
+        return lds
+    _f32(table, "table")
+    if tuple(table.shape) != (H, index.n_offsets) or not table.is_contiguous():
+        raise NrvError(f"bias_attn: table must be contiguous [{H}, {index.n_offsets}], got {tuple(table.shape)}")
+    for t, n, name in ((index.idx, Nq * Nk, "index.idx"), (index.inv_ptr, index.n_offsets + 1, "index.inv_ptr"),
+                       (index.inv_pos, Nq * Nk, "index.inv_pos")):
+        _dense(t, name, torch.int32, n, "Nq, Nk and the table")
+    if tuple(index.idx.shape) != (Nq, Nk):
+        raise NrvError(f"bias_attn: index.idx {tuple(index.idx.shape)} does not belong to ({Nq}, {Nk})")
+    return lds
 
 
 def bias_attn_fwd(q: Tensor, k: Tensor, v: Tensor, hq: int, hk: int, hv: int, table: Tensor, index: BiasIndex,
                   B: int, H: int, Nq: int, Nk: int, kd: int, d: int, robust: bool):
     """q / k / v: [B*Nq|Nk, *] bf16 views whose first column is head 0's q / k / v, heads hq / hk / hv columns apart
     (include/nrv.h nrv_bias_attn_fwd).  Returns (o bf16 [B*Nq, H*d], hardswish(o) bf16, stats fp32 [B*H, S])."""
-    ldq = _qkv_view(q, B * Nq, "q"); ldk = _qkv_view(k, B * Nk, "k"); ldv = _qkv_view(v, B * Nk, "v")
-    _f32(table, "table")
-    if tuple(table.shape) != (H, index.n_offsets) or not table.is_contiguous():
-        raise NrvError(f"bias_attn: table must be contiguous [{H}, {index.n_offsets}], got {tuple(table.shape)}")
-    if tuple(index.idx.shape) != (Nq, Nk):
-        raise NrvError(f"bias_attn: index {tuple(index.idx.shape)} does not belong to ({Nq}, {Nk})")
+    ldq, ldk, ldv = _bias_attn_args(q, k, v, hq, hk, hv, table, index, B, H, Nq, Nk, kd, d)
     lib = _lib.load()
     S = lib.nrv_bias_attn_stats_size(Nq, Nk, int(bool(robust)))
     o = torch.empty(B * Nq, H * d, dtype=torch.bfloat16, device=q.device)
@@ -1278,16 +1364,15 @@ def bias_attn_bwd(q: Tensor, k: Tensor, v: Tensor, hq: int, hk: int, hv: int, ta
                   o: Tensor, dact: Tensor, stats: Tensor, dq: Tensor, dk: Tensor, dv: Tensor,
                   B: int, H: int, Nq: int, Nk: int, kd: int, d: int, robust: bool) -> Tensor:
     """Writes dq / dk / dv (views laid out like q / k / v) and returns dtable fp32 [H, n_offsets]; deterministic."""
-    ldq = _qkv_view(q, B * Nq, "q"); ldk = _qkv_view(k, B * Nk, "k"); ldv = _qkv_view(v, B * Nk, "v")
-    if _qkv_view(dq, B * Nq, "dq") != ldq or _qkv_view(dk, B * Nk, "dk") != ldk or _qkv_view(dv, B * Nk, "dv") != ldv:
-        raise NrvError("bias_attn_bwd: the gradients must be laid out like q / k / v")
+    ldq, ldk, ldv = _bias_attn_args(q, k, v, hq, hk, hv, table, index, B, H, Nq, Nk, kd, d)
+    if _bias_attn_args(dq, dk, dv, hq, hk, hv, table, index, B, H, Nq, Nk, kd, d, pre="d") != (ldq, ldk, ldv):
+        raise NrvError("bias_attn_bwd: the gradients dq / dk / dv must be laid out (row strides) like q / k / v")
     for t, n in ((o, "o"), (dact, "dact")):
         _bf16(t, n)
         if tuple(t.shape) != (B * Nq, H * d) or not t.is_contiguous():
             raise NrvError(f"bias_attn_bwd: {n} must be contiguous [{B * Nq}, {H * d}]")
     lib = _lib.load()
-    if tuple(stats.shape) != (B * H, lib.nrv_bias_attn_stats_size(Nq, Nk, int(bool(robust)))):
-        raise NrvError("bias_attn_bwd: stats do not belong to this call")
+    _dense(stats, "stats", torch.float32, B * H * lib.nrv_bias_attn_stats_size(Nq, Nk, int(bool(robust))), "the forward of this call")
     wsb = lib.nrv_bias_attn_bwd_workspace(B, H, index.n_offsets)
     ws = _workspace(wsb, q.device)
     dtable = torch.empty_like(table)
@@ -1310,13 +1395,22 @@ def _gelu_stream(g: Optional[Tensor], rows: int, C: int) -> Tuple[Optional[int],
         return None, NRV_BF16
     _dev(g, "gelu_stream")
     if g.dtype == torch.uint8:
-        if C % 64 or g.numel() < (rows + 1) // 2 * 2 * C:
-            raise NrvError("the 8-bit gelu' stream is stored in row pairs: C % 64 == 0 and an even row count")
+        if C % 64 or g.numel() < (rows + 1) // 2 * 2 * C or not g.is_contiguous():
+            raise NrvError(f"gelu_stream: the 8-bit gelu' stream is contiguous and stored in row pairs, C % 64 == 0 and an even row "
+                           f"count; got {tuple(g.shape)} stride {g.stride()} for [{rows}, {C}]")
         return g.data_ptr(), NRV_U8
     _bf16(g, "gelu_stream")
-    if tuple(g.shape) != (rows, C) or not g.is_contiguous():
-        raise NrvError(f"gelu' stream must be contiguous [{rows}, {C}], got {tuple(g.shape)}")
+    if g.numel() != rows * C or not g.is_contiguous():
+        raise NrvError(f"gelu_stream must be contiguous [{rows}, {C}], got {tuple(g.shape)} stride {g.stride()}")
     return g.data_ptr(), NRV_BF16
+
+
+def _taps(w: Tensor, name: str, rows: int, cols: int, by: str = "the call's dimensions") -> Tensor:
+    """A weight of rows * cols fp32 elements (Conv2d-shaped or flat) as a contiguous [rows, cols]; a strided one is copied."""
+    _f32(w, name)
+    if w.numel() != rows * cols:
+        raise NrvError(f"{name} must hold {rows} x {cols} fp32 elements (by {by}), got {tuple(w.shape)}")
+    return w.reshape(rows, cols).contiguous()
 
 
 def _pcn_rows(a: Tensor, B: int, HW: int, C: int, name: str) -> None:
@@ -1328,8 +1422,8 @@ def _pcn_rows(a: Tensor, B: int, HW: int, C: int, name: str) -> None:
 def dwconv3x3_fwd(a: Tensor, w: Tensor, bias: Tensor, B: int, H: int, W: int):
     """(d bf16 [B*H*W, C] = gelu(dwconv3x3(a) + bias), sq fp32 [B, C] = per-sample channel sums of d)."""
     C = a.shape[1]
-    _pcn_rows(a, B, H * W, C, "a"); _f32(w, "w"); _f32(bias, "bias")
-    w = w.reshape(C, 9).contiguous()
+    _pcn_rows(a, B, H * W, C, "a")
+    w = _taps(w, "w", C, 9, "a"); _dense(bias, "bias", torch.float32, C, "a")
     d = torch.empty_like(a)
     sq = torch.empty(B, C, dtype=torch.float32, device=a.device)
     _run("dwconv3x3_fwd", 18.0 * a.numel(), 4 * a.numel(),
@@ -1343,9 +1437,10 @@ def dwconv3x3_bwd(a: Tensor, w: Tensor, bias: Tensor, dg: Tensor, s: Tensor, dme
     """(da bf16 [B*H*W, C] (times gelu_stream when given), dw fp32 [C, 1, 3, 3], db fp32 [C])."""
     C = a.shape[1]
     _pcn_rows(a, B, H * W, C, "a"); _pcn_rows(dg, B, H * W, C, "dg")
-    _f32(w, "w"); _f32(bias, "bias"); _f32(s, "s"); _f32(dmean, "dmean")
+    _dense(bias, "bias", torch.float32, C, "a"); _dense(s, "s", torch.float32, B * C, "B and a")
+    _dense(dmean, "dmean", torch.float32, B * C, "B and a")
     gp, gdt = _gelu_stream(gelu_stream, B * H * W, C)
-    w9 = w.reshape(C, 9).contiguous()
+    w9 = _taps(w, "w", C, 9, "a")
     da = torch.empty_like(a)
     dw = torch.empty(C, 9, dtype=torch.float32, device=a.device)
     db = torch.empty(C, dtype=torch.float32, device=a.device)
@@ -1360,12 +1455,11 @@ def dwconv3x3_bwd(a: Tensor, w: Tensor, bias: Tensor, dg: Tensor, s: Tensor, dme
 
 def se_fwd(sq: Tensor, HW: int, wr: Tensor, br: Tensor, we: Tensor, be: Tensor):
     """(s fp32 [B, C] = sigmoid(W_e relu(W_r sq / HW + b_r) + b_e), hid fp32 [B, rd])."""
-    _f32(sq, "sq")
+    _dense(sq, "sq", torch.float32, sq.numel())
     B, C = sq.shape
     rd = wr.shape[0]
-    for t, n in ((wr, "wr"), (br, "br"), (we, "we"), (be, "be")):
-        _f32(t, n)
-    wr2, we2 = wr.reshape(rd, C).contiguous(), we.reshape(C, rd).contiguous()
+    wr2, we2 = _taps(wr, "wr", rd, C, "sq"), _taps(we, "we", C, rd, "wr and sq")
+    _dense(br, "br", torch.float32, rd, "wr"); _dense(be, "be", torch.float32, C, "sq")
     hid = torch.empty(B, rd, dtype=torch.float32, device=sq.device)
     s = torch.empty(B, C, dtype=torch.float32, device=sq.device)
     _run("se_fwd", 4.0 * B * C * rd, 8 * C * rd,
@@ -1376,8 +1470,9 @@ def se_fwd(sq: Tensor, HW: int, wr: Tensor, br: Tensor, we: Tensor, be: Tensor):
 
 def se_apply(d: Tensor, s: Tensor, HW: int) -> Tensor:
     """g bf16 = d * s[sample] (SqueezeExcite's x * gate)."""
+    _dense(s, "s", torch.float32, s.numel())
     B, C = s.shape
-    _pcn_rows(d, B, HW, C, "d"); _f32(s, "s")
+    _pcn_rows(d, B, HW, C, "d")
     g = torch.empty_like(d)
     _run("se_apply", 0.0, 4 * d.numel(),
          lambda: _lib.load().nrv_se_apply(d.data_ptr(), s.data_ptr(), g.data_ptr(), B, int(HW), C, _stream()), "nrv_se_apply")
@@ -1386,10 +1481,12 @@ def se_apply(d: Tensor, s: Tensor, HW: int) -> Tensor:
 
 def se_bwd(dg: Tensor, d: Tensor, sq: Tensor, HW: int, s: Tensor, hid: Tensor, wr: Tensor, we: Tensor):
     """(dmean fp32 [B, C], dW_r, db_r, dW_e, db_e) with the weight gradients in the Conv2d shapes of wr / we."""
+    _dense(s, "s", torch.float32, s.numel())
     B, C = s.shape
     rd = hid.shape[1]
     _pcn_rows(dg, B, HW, C, "dg"); _pcn_rows(d, B, HW, C, "d")
-    wr2, we2 = wr.reshape(rd, C).contiguous(), we.reshape(C, rd).contiguous()
+    _dense(sq, "sq", torch.float32, B * C, "s"); _dense(hid, "hid", torch.float32, B * rd, "s")
+    wr2, we2 = _taps(wr, "wr", rd, C, "hid and s"), _taps(we, "we", C, rd, "hid and s")
     dev = d.device
     dmean = torch.empty(B, C, dtype=torch.float32, device=dev)
     dwr = torch.empty(rd, C, dtype=torch.float32, device=dev)
@@ -1417,12 +1514,13 @@ def _ls_keep(keep: Optional[Tensor], rows: int) -> int:
 def ls_add(x: Tensor, y: Tensor, gamma: Tensor, keep: Optional[Tensor] = None, survival: float = 1.0,
            out: Optional[Tensor] = None) -> Tensor:
     """out fp32 = x + f * gamma * y, f = keep[sample] / survival (or 1)."""
-    _f32(x, "x"); _f32(y, "y"); _f32(gamma, "gamma")
-    if not x.is_contiguous() or y.shape != x.shape or not y.is_contiguous():
-        raise NrvError("ls_add: x and y must be contiguous fp32 [rows, C] of one shape")
+    _dense(x, "x", torch.float32, x.numel())
     rows, C = x.shape
+    _dense(y, "y", torch.float32, rows * C, "x"); _dense(gamma, "gamma", torch.float32, C, "x")
     per = _ls_keep(keep, rows)
     o = torch.empty_like(x) if out is None else out
+    if out is not None:
+        _dense(out, "out", torch.float32, rows * C, "x")
     _run("ls_add", 0.0, 12 * x.numel(),
          lambda: _lib.load().nrv_ls_add_f32(x.data_ptr(), y.data_ptr(), gamma.data_ptr(), _ptr(keep), float(survival), o.data_ptr(),
                                             rows, per, C, _stream()), "nrv_ls_add_f32")
@@ -1431,10 +1529,9 @@ def ls_add(x: Tensor, y: Tensor, gamma: Tensor, keep: Optional[Tensor] = None, s
 
 def ls_bwd(dy: Tensor, y: Tensor, gamma: Tensor, keep: Optional[Tensor] = None, survival: float = 1.0):
     """(dz bf16 = dy * f * gamma, dgamma fp32 [C] = sum_rows dy * f * y)."""
-    _f32(dy, "dy"); _f32(y, "y"); _f32(gamma, "gamma")
-    if not dy.is_contiguous() or y.shape != dy.shape or not y.is_contiguous():
-        raise NrvError("ls_bwd: dy and y must be contiguous fp32 [rows, C] of one shape")
+    _dense(dy, "dy", torch.float32, dy.numel())
     rows, C = dy.shape
+    _dense(y, "y", torch.float32, rows * C, "dy"); _dense(gamma, "gamma", torch.float32, C, "dy")
     per = _ls_keep(keep, rows)
     dz = torch.empty(rows, C, dtype=torch.bfloat16, device=dy.device)
     dgamma = torch.empty(C, dtype=torch.float32, device=dy.device)
@@ -1458,20 +1555,27 @@ def dgelu_rows(dx: Tensor, gelu_stream: Tensor) -> Tensor:
     return out
 
 
-def _ca_view(t: Optional[Tensor], rows: int, name: str) -> int:
+def _ca_view(t: Optional[Tensor], rows: int, width: int, name: str) -> int:
     if t is None:
         return 0
     _bf16(t, name)
-    if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] < rows:
-        raise NrvError(f"{name}: bf16 rows [>= {rows}, C] with contiguous columns, got {tuple(t.shape)} stride {t.stride()}")
+    if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] < rows or t.shape[1] < width or (t.shape[0] > 1 and t.stride(0) < width):
+        raise NrvError(f"{name}: bf16 rows [>= {rows}, >= {width}] with contiguous columns, got {tuple(t.shape)} stride {t.stride()}")
     return t.stride(0)
+
+
+def _cls_attn_args(q: Tensor, kc: Tensor, kp: Optional[Tensor], vc: Tensor, vp: Optional[Tensor], B: int, heads: int, Np: int, dh: int):
+    if Np > 0 and (kp is None or vp is None):
+        raise NrvError(f"cls_attn: {Np} patch keys need kp and vp")
+    W = heads * dh
+    return (_ca_view(q, B, W, "q"), _ca_view(kc, B, W, "kc"), _ca_view(vc, B, W, "vc"),
+            _ca_view(kp, B * Np, W, "kp"), _ca_view(vp, B * Np, W, "vp"))
 
 
 def cls_attn_fwd(q: Tensor, kc: Tensor, kp: Optional[Tensor], vc: Tensor, vp: Optional[Tensor], B: int, heads: int, Np: int,
                  dh: int, scale: float):
     """(o bf16 [B, heads*dh], lse fp32 [B*heads]): one query per sample against the class key and its Np patch keys."""
-    lq, lkc, lvc = _ca_view(q, B, "q"), _ca_view(kc, B, "kc"), _ca_view(vc, B, "vc")
-    lkp, lvp = _ca_view(kp, B * Np, "kp"), _ca_view(vp, B * Np, "vp")
+    lq, lkc, lvc, lkp, lvp = _cls_attn_args(q, kc, kp, vc, vp, B, heads, Np, dh)
     o = torch.empty(B, heads * dh, dtype=torch.bfloat16, device=q.device)
     lse = torch.empty(B * heads, dtype=torch.float32, device=q.device)
     _run("cls_attn_fwd", 4.0 * B * heads * (Np + 1) * dh, 4 * B * (Np + 1) * heads * dh,
@@ -1484,9 +1588,8 @@ def cls_attn_fwd(q: Tensor, kc: Tensor, kp: Optional[Tensor], vc: Tensor, vp: Op
 def cls_attn_bwd(q: Tensor, kc: Tensor, kp: Optional[Tensor], vc: Tensor, vp: Optional[Tensor], dout: Tensor, lse: Tensor,
                  B: int, heads: int, Np: int, dh: int, scale: float):
     """(dq, dkc, dkp, dvc, dvp), bf16, each shaped like its input."""
-    lq, lkc, lvc = _ca_view(q, B, "q"), _ca_view(kc, B, "kc"), _ca_view(vc, B, "vc")
-    lkp, lvp = _ca_view(kp, B * Np, "kp"), _ca_view(vp, B * Np, "vp")
-    _ca_view(dout, B, "dout"); _f32(lse, "lse")
+    lq, lkc, lvc, lkp, lvp = _cls_attn_args(q, kc, kp, vc, vp, B, heads, Np, dh)
+    _ca_view(dout, B, heads * dh, "dout"); _dense(lse, "lse", torch.float32, B * heads, "B and heads")
     # the kernel writes each gradient with its input's leading dimension: same strides
     outs = [torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=t.device) if t is not None else None
             for t in (q, kc, kp, vc, vp)]
@@ -1513,20 +1616,22 @@ def _th_args(t: Tensor, W: Tuple[Tensor, ...], name: str) -> Tuple[int, int, int
     if t.dim() != 4 or not t.is_contiguous():
         raise NrvError(f"{name} must be a contiguous fp32 [B, H, Nq, Nk] matrix, got {tuple(t.shape)}")
     B, H, Nq, Nk = t.shape
-    for w in W:
-        _f32(w, "mixing matrix")
+    for i, w in enumerate(W):
+        wn = "W" if len(W) == 1 else f"W{i + 1}"
+        _f32(w, wn)
         if tuple(w.shape) != (H, H) or not w.is_contiguous():
-            raise NrvError(f"the head-mixing matrix must be contiguous fp32 [{H}, {H}], got {tuple(w.shape)}")
+            raise NrvError(f"{wn}: the head-mixing matrix must be contiguous fp32 [{H}, {H}] (H by {name}), got {tuple(w.shape)} "
+                           f"stride {w.stride()}")
     if not th_shape_ok(H, Nq, Nk):
         raise NotImplementedError(f"talking-heads kernels: {H} heads, {Nq} x {Nk} scores; they take at most {TH_MAX_HEADS} heads and "
                                   f"{TH_MAX_KEYS} keys")
     return B, H, Nq, Nk
 
 
-def _th_like(t: Tensor, other: Tensor, name: str) -> None:
+def _th_like(t: Tensor, tname: str, other: Tensor, name: str) -> None:
     _f32(other, name)
     if other.shape != t.shape or not other.is_contiguous():
-        raise NrvError(f"{name} must be contiguous fp32 of shape {tuple(t.shape)}, got {tuple(other.shape)}")
+        raise NrvError(f"{name} must be contiguous fp32 of {tname}'s shape {tuple(t.shape)}, got {tuple(other.shape)} stride {other.stride()}")
 
 
 def th_softmax_fwd(S: Tensor, W1: Tensor, W2: Tensor, a_dtype: torch.dtype = torch.bfloat16):
@@ -1544,7 +1649,7 @@ def th_softmax_fwd(S: Tensor, W1: Tensor, W2: Tensor, a_dtype: torch.dtype = tor
 def th_softmax_bwd(dA: Tensor, P: Tensor, S: Tensor, W1: Tensor, W2: Tensor):
     """(dS fp32, dW1, dW2) of th_softmax_fwd from dA fp32 (= dO v^T)."""
     B, H, Nq, Nk = _th_args(S, (W1, W2), "S")
-    _th_like(S, dA, "dA"); _th_like(S, P, "P")
+    _th_like(S, "S", dA, "dA"); _th_like(S, "S", P, "P")
     dS = torch.empty_like(S)
     dW1 = torch.empty(H, H, dtype=torch.float32, device=S.device)
     dW2 = torch.empty(H, H, dtype=torch.float32, device=S.device)
@@ -1571,7 +1676,7 @@ def head_mix_fwd(x: Tensor, W: Tensor, out_dtype: torch.dtype = torch.float32) -
 def head_mix_bwd(dout: Tensor, x: Tensor, W: Tensor):
     """(din fp32, dW fp32 [H, H]) of head_mix_fwd."""
     B, H, Nq, Nk = _th_args(x, (W,), "x")
-    _th_like(x, dout, "dout")
+    _th_like(x, "x", dout, "dout")
     din = torch.empty_like(x)
     dW = torch.empty(H, H, dtype=torch.float32, device=x.device)
     lib = _lib.load()
@@ -1585,10 +1690,8 @@ def head_mix_bwd(dout: Tensor, x: Tensor, W: Tensor):
 # ---- re-attention on materialised [B,H,Nq,Nk] matrices (DeepViT, deepvit.py:47-53, 67-74; include/nrv.h) -----------------
 def _ra_args(t: Tensor, W: Tensor, vecs: Tuple[Tensor, ...], eps: float, name: str) -> Tuple[int, int, int, int]:
     B, H, Nq, Nk = _th_args(t, (W,), name)
-    for v in vecs:
-        _f32(v, "reattn_norm weight / bias")
-        if tuple(v.shape) != (H,) or not v.is_contiguous():
-            raise NrvError(f"the LayerNorm over heads takes contiguous fp32 [{H}] vectors, got {tuple(v.shape)}")
+    for v, vn in zip(vecs, ("gamma", "beta")):
+        _dense(v, vn, torch.float32, H, name)
     if not eps > 0:
         raise NotImplementedError(f"re-attention kernels: eps must be positive, got {eps}")
     return B, H, Nq, Nk
@@ -1613,7 +1716,7 @@ def reattn_softmax_fwd(S: Tensor, W: Tensor, gamma: Tensor, beta: Tensor, eps: f
 def reattn_softmax_bwd(dA: Tensor, P: Tensor, W: Tensor, gamma: Tensor, eps: float):
     """(dS fp32, dW [H, H], dgamma [H], dbeta [H]) of reattn_softmax_fwd from dA fp32 (= dO v^T) and the kept P."""
     B, H, Nq, Nk = _ra_args(P, W, (gamma,), eps, "P")
-    _th_like(P, dA, "dA")
+    _th_like(P, "P", dA, "dA")
     dS = torch.empty_like(P)
     dW, dg, db = _ra_grads(H, P.device)
     lib = _lib.load()
@@ -1639,7 +1742,7 @@ def reattn_norm_fwd(P: Tensor, W: Tensor, gamma: Tensor, beta: Tensor, eps: floa
 def reattn_norm_bwd(dA: Tensor, P: Tensor, W: Tensor, gamma: Tensor, eps: float):
     """(dP fp32, dW [H, H], dgamma [H], dbeta [H]) of reattn_norm_fwd; dP goes to sinkhorn_bwd."""
     B, H, Nq, Nk = _ra_args(P, W, (gamma,), eps, "P")
-    _th_like(P, dA, "dA")
+    _th_like(P, "P", dA, "dA")
     dP = torch.empty_like(P)
     dW, dg, db = _ra_grads(H, P.device)
     lib = _lib.load()
@@ -1703,10 +1806,11 @@ def soft_split_bwd(dcols: Tensor, B: int, C: int, H: int, W: int, ks: int, strid
 
 def layernorm_pad_fwd(x: Tensor, n: int, gamma: Tensor, beta: Tensor, eps: float):
     """x [rows, ld] fp32|bf16 with n true columns -> (y bf16 [rows, ld] with zero pad columns, mean, rstd)."""
-    _dev(x, "x"); _f32(gamma, "gamma"); _f32(beta, "beta")
+    _dev(x, "x")
     rows, _, ld = _rows2d(x, "x")
-    if x.shape[1] != ld or gamma.numel() != n or beta.numel() != n:
-        raise NrvError(f"layernorm_pad_fwd: x must be dense [rows, ld] and gamma / beta hold n = {n} elements")
+    if x.shape[1] != ld or not 0 < n <= ld:
+        raise NrvError(f"layernorm_pad_fwd: x must be dense [rows, ld] with n = {n} <= ld true columns, got {tuple(x.shape)} stride {x.stride()}")
+    _dense(gamma, "gamma", torch.float32, n, "n"); _dense(beta, "beta", torch.float32, n, "n")
     y = torch.empty(rows, ld, dtype=torch.bfloat16, device=x.device)
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
@@ -1721,12 +1825,14 @@ def layernorm_pad_fwd(x: Tensor, n: int, gamma: Tensor, beta: Tensor, eps: float
 def layernorm_pad_bwd(dy: Tensor, x: Tensor, n: int, gamma: Tensor, mean: Tensor, rstd: Tensor, dres: Optional[Tensor] = None,
                       want_f32: bool = True, want_bf16: bool = False):
     """(dx_f32|None, dx_bf16|None, dgamma [n], dbeta [n]); dx = dres + LN'(dy) on the n true columns, zero pad columns."""
-    _bf16(dy, "dy"); _dev(x, "x"); _f32(gamma, "gamma"); _f32(mean, "mean"); _f32(rstd, "rstd")
+    _dev(x, "x")
     rows, _, ld = _rows2d(x, "x")
-    if x.shape[1] != ld or tuple(dy.shape) != (rows, ld) or not dy.is_contiguous() or gamma.numel() != n:
-        raise NrvError("layernorm_pad_bwd: x and dy must be dense [rows, ld], gamma holds n elements")
-    if dres is not None and (tuple(dres.shape) != (rows, ld) or not dres.is_contiguous()):
-        raise NrvError("layernorm_pad_bwd: dres must be dense [rows, ld]")
+    if x.shape[1] != ld or not 0 < n <= ld:
+        raise NrvError(f"layernorm_pad_bwd: x must be dense [rows, ld] with n = {n} <= ld true columns, got {tuple(x.shape)} stride {x.stride()}")
+    _dense(dy, "dy", torch.bfloat16, rows * ld, "x"); _dense(gamma, "gamma", torch.float32, n, "n")
+    _dense(mean, "mean", torch.float32, rows, "x"); _dense(rstd, "rstd", torch.float32, rows, "x")
+    if dres is not None:
+        _dense(dres, "dres", None, rows * ld, "x")
     if not (want_f32 or want_bf16):
         raise NrvError("layernorm_pad_bwd: nothing asked for")
     lib = _lib.load()
@@ -1762,11 +1868,7 @@ def attn_wide_fwd(qkv: Tensor, B: int, N: int, H: int, dh: int, scale: float):
 
 
 def attn_wide_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, B: int, N: int, H: int, dh: int, scale: float) -> Tensor:
-    _bf16(qkv, "qkv"); _bf16(out, "out"); _bf16(dout, "dout"); _f32(lse, "lse")
-    if not (qkv.is_contiguous() and out.is_contiguous() and dout.is_contiguous() and lse.is_contiguous()):
-        raise NrvError("attn_wide_bwd: operands must be contiguous")
-    if qkv.numel() != B * N * 3 * H * dh or out.numel() != B * N * H * dh or dout.numel() != out.numel() or lse.numel() != B * H * N:
-        raise NrvError("attn_wide_bwd: operand sizes do not match B, N, H, dh")
+    _attn_bwd_args(qkv, out, dout, lse, B, N, H, dh)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(B * H * N, dtype=torch.float32, device=qkv.device)
     lib = _lib.load()
@@ -1780,10 +1882,8 @@ def attn_wide_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, B: int, N
 # ----------------------------------------------------------------------------------------------
 # RvT (ABI 18, added entry points): axial rotary embedding, plain depthwise ks x ks conv on rows with class rows, GEGLU
 # ----------------------------------------------------------------------------------------------
-def _rotary(fn: str, qkv: Tensor, sin: Tensor, cos: Tensor, B: int, N: int, lead: int, H: int, dh: int) -> Tensor:
-    _bf16(qkv, "qkv"); _f32(sin, "sin"); _f32(cos, "cos")
-    if not qkv.is_contiguous() or qkv.numel() != B * N * 3 * H * dh:
-        raise NrvError(f"{fn}: qkv must be contiguous [B*N, 3*H*dh]")
+def _rotary(fn: str, qkv: Tensor, sin: Tensor, cos: Tensor, B: int, N: int, lead: int, H: int, dh: int, name: str = "qkv") -> Tensor:
+    _dense(qkv, name, torch.bfloat16, B * N * 3 * H * dh); _f32(sin, "sin"); _f32(cos, "cos")
     if sin.dim() != 2 or sin.shape != cos.shape or sin.shape[0] != N - lead or not (sin.is_contiguous() and cos.is_contiguous()):
         raise NrvError(f"{fn}: sin / cos must be contiguous fp32 [{N - lead}, dr / 2], got {tuple(sin.shape)} / {tuple(cos.shape)}")
     dr = 2 * sin.shape[1]
@@ -1801,7 +1901,7 @@ def rotary_fwd(qkv: Tensor, sin: Tensor, cos: Tensor, B: int, N: int, lead: int,
 
 def rotary_bwd(dqkv: Tensor, sin: Tensor, cos: Tensor, B: int, N: int, lead: int, H: int, dh: int) -> Tensor:
     """The transposed rotation, in place on dqkv."""
-    return _rotary("nrv_rotary_bwd", dqkv, sin, cos, B, N, lead, H, dh)
+    return _rotary("nrv_rotary_bwd", dqkv, sin, cos, B, N, lead, H, dh, "dqkv")
 
 
 def _dwc_args(a: Tensor, w: Tensor, B: int, H: int, W: int, lead: int, name: str) -> Tuple[int, int, Tensor]:
@@ -2044,9 +2144,8 @@ def layernorm_f32_bwd(dy: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: 
                       dx: Optional[Tensor] = None, dx_bf16: Optional[Tensor] = None):
     """(dx fp32, dx bf16 | None, dgamma, dbeta) from an fp32 dy (include/nrv.h nrv_layernorm_f32_bwd)."""
     rows, dim = _lnf_args("layernorm_f32_bwd", x, gamma, None)
-    _f32(dy, "dy"); _f32(mean, "mean"); _f32(rstd, "rstd")
-    if dy.shape != x.shape or not dy.is_contiguous() or mean.numel() != rows or rstd.numel() != rows:
-        raise NrvError("layernorm_f32_bwd: dy must match x, mean and rstd hold one value per row")
+    _dense(dy, "dy", torch.float32, rows * dim, "x"); _dense(mean, "mean", torch.float32, rows, "x")
+    _dense(rstd, "rstd", torch.float32, rows, "x")
     dx = _out_buffer(dx, (rows, dim), torch.float32, x.device, "dx")
     dx16 = _out_buffer(dx_bf16, (rows, dim), torch.bfloat16, x.device, "dx_bf16") if (want_bf16 or dx_bf16 is not None) else None
     dg = torch.empty(dim, dtype=torch.float32, device=x.device)
